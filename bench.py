@@ -14,11 +14,18 @@ decision -- exactly the phases satba/trf.py runs per iteration, with the same al
 readbacks.  Inputs are resident in HBM before the timed region.  With N > 1 the SAME problem is sharded by
 points over the ranks (strong scaling); value = steps / max-over-ranks wall time.
 
-One JSON line is printed by rank 0; see DESIGN.md for `roofline` (fused residual+Jacobian kernel, algorithmic
-bytes 48 K + 96 N per launch) and `cpu_baseline` (the reference's scipy path restated in oracle/, timed on this host:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the steps and prints the line (metric, value,
+unit, ms_per_step, ...).  --full adds what takes passes of its own after the timed steps; see DESIGN.md for `roofline`
+(fused residual+Jacobian kernel, algorithmic bytes 48 K + 96 N per launch), `kernel_ms`, `phase_ms` (N > 1), `e2e` (the
+drop-in call) and `cpu_baseline` (the reference's scipy path restated in oracle/, timed on this host:
 the full solve at the C2 shape and one LM iteration on a bounded sub-problem of the benchmarked scene, scaled linearly in
 the number of observations -- a lower bound on the CPU time, LSMR needs more iterations on larger problems; the measured
 C3 run of BASELINE.md section 3 is quoted from profiles/ when it has been taken).
+
+--dump-outputs DIR writes what the last timed step left to its caller, as float64 .npy files: the point (x_cameras.npy:
+camera parameters, x_points.npy: 3-D points, all ranks gathered), cost.npy (the cost at that point) and trust_radius.npy
+(the radius the next step would start from).  The inputs are generated from a fixed seed, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -215,6 +222,23 @@ def cpu_baseline(scene, n_pts_sample, corr, full_c3=False):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, p, x, cost, delta):
+    """The state the last timed step hands its caller, as DIR/<name>.npy (float64); x is the whole point (all ranks)."""
+    n_c = p.n_cam * p.n_params
+    arrays = {"x_cameras": x[:n_c].reshape(p.n_cam, p.n_params), "x_points": x[n_c:].reshape(-1, 3),
+              "cost": np.array([cost]), "trust_radius": np.array([delta])}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:  # the largest shape (C4: 1 M points) writes 24 MB
+        raise SystemExit("--dump-outputs: {} bytes exceed the {} byte limit".format(total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,13 +256,18 @@ def main():
     ap.add_argument("--driver", default="auto", help="host side of an LM iteration: native (device-resident loop, satba_lm_ticks; one rank) | device (the same for several ranks: tick parts + queued all-reduces) | "
                     "native-sync (C++ host loop, satba_lm_step: two header reads per iteration) | python (phase entry points + all-reduces) | "
                     "auto (native for one rank, device for several)")
-    ap.add_argument("--cpu-c3", action="store_true", help="also run the measured C3 CPU baseline (max_nfev=3, ~10 min)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline does not need: the roofline "
+                    "pass over k_linearize, kernel_ms, phase_ms (several ranks), e2e (unless --no-e2e) and cpu_baseline (unless "
+                    "--cpu-sample-pts 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the point, cost and trust radius after the last timed step to DIR/*.npy")
+    ap.add_argument("--cpu-c3", action="store_true", help="also run the measured C3 CPU baseline (max_nfev=3, ~10 min; implies --full)")
     ap.add_argument("--backend", default="nccl", help="collective backend for several ranks: nccl (= RCCL; what the scaling runs use) | gloo (tests)")
     ap.add_argument("--share-gpu", action="store_true", help="tests: all ranks on GPU 0 (a one-GPU box; needs --backend gloo)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the wall clock of the drop-in call (ba_core.run_ba_optimization) after the timed loop")
     ap.add_argument("--camera-major", action="store_true", help="form the per-camera sums with the camera-major float64 pass from the "
                     "start (SATBA_FLAG_CAMERA_MAJOR_SUMS: the route the fixed-point sums fall back to)")
     args = ap.parse_args()
+    full = args.full or args.cpu_c3
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -378,29 +407,35 @@ def main():
     ls = run(args.steps)
     sync()
     dt = time.perf_counter() - t0
-    # the roofline kernel inside LM iterations: a second pass over the same iterations with HIP events around every k_linearize
-    # launch, on its launch stream (the timed pass itself carries no events)
-    if restart:
-        eng.snapshot_x(True)
-        st["first"] = True
-    n_step[0] = 0
-    keep = dict(st)
-    eng.profile_linearize(True)
-    run(min(args.steps, 40))
-    n_lin, ms_lin = eng.profile_read()
-    eng.profile_linearize(False)
-    st.clear()
-    st.update(keep)
     if ticks or driver == "device":
         if int(ls["phase"]) == 2:
             raise SystemExit("the device-resident loop stopped for the host (reason {}): use --driver native-sync".format(int(ls["host_reason"])))
         assert int(ls["iterations"]) == args.steps, ls
         st.update(accepted=int(ls["accepted"]), interior=int(ls["newton"]), cost=ls["cost_new"] if ls["actual"] > 0 else ls["cost"])
-    phase_ms = None
+    if args.dump_outputs:
+        x = sharding.assemble_x(p, eng.shard, eng.get_x(), comm)  # (several ranks: a collective, every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, p, x, st["cost"], ls["Delta"] if ls else st["Delta"])
+    n_lin = ms_lin = kern = phase_ms = None
+    if full:
+        # the roofline kernel inside LM iterations: a second pass over the same iterations with HIP events around every k_linearize
+        # launch, on its launch stream (the timed pass itself carries no events)
+        if restart:
+            eng.snapshot_x(True)
+            st["first"] = True
+        n_step[0] = 0
+        keep = dict(st)
+        eng.profile_linearize(True)
+        run(min(args.steps, 40))
+        n_lin, ms_lin = eng.profile_read()
+        eng.profile_linearize(False)
+        st.clear()
+        st.update(keep)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and full:
         # where an iteration's time goes with several ranks: a second pass over the same iterations, every
         # phase and every collective between torch events on the stream they are queued on, the blocking header reads on the
         # host's clock; rank 0's figures, ms per iteration.  ("dense_solve" includes the scaling of the reduced system and the
@@ -422,37 +457,21 @@ def main():
         st.clear()
         st.update(keep2)
 
-    # dominant kernels, HIP events on the launch stream (rank-local shard)
-    eng.linearize()
-    comm.allreduce(eng, eng.len_lin)
-    eng.prepare(False)
-    eng.schur(1e-6)
-    kern = {}
-    for name in ("linearize", "residual", "jvp", "backsub", "schur", "cholesky"):
-        eng.linearize(); eng.prepare(False); eng.schur(1e-6)
-        kern[name] = eng.time_kernel(name, args.kernel_reps if name not in ("schur", "cholesky") else max(2, args.kernel_reps // 5))
-    torch.cuda.synchronize()
+    if full:
+        # dominant kernels, HIP events on the launch stream (rank-local shard)
+        eng.linearize()
+        comm.allreduce(eng, eng.len_lin)
+        eng.prepare(False)
+        eng.schur(1e-6)
+        kern = {}
+        for name in ("linearize", "residual", "jvp", "backsub", "schur", "cholesky"):
+            eng.linearize(); eng.prepare(False); eng.schur(1e-6)
+            kern[name] = eng.time_kernel(name, args.kernel_reps if name not in ("schur", "cholesky") else max(2, args.kernel_reps // 5))
+        torch.cuda.synchronize()
 
     if rank == 0:
         K_loc, N_loc = eng.n_obs, eng.n_pts
-        alg_bytes = 48.0 * K_loc + 96.0 * N_loc
-        # the roofline kernel's duration: average over its launches INSIDE the timed LM iterations (HIP events on the launch
-        # stream); kernel_ms["linearize"] is the same kernel in 20 back-to-back launches after the loop (a few % slower: the loop
-        # leaves part of the working set in the Infinity Cache)
-        t_lin = (ms_lin / n_lin if n_lin else kern["linearize"]) * 1e-3
-        achieved = alg_bytes / t_lin / 1e9
-        traffic = profiled_traffic(args.shape, args.loss, world)
         info = eng.info()
-        comp_bytes = compulsory_bytes(K_loc, N_loc, model, p.n_params, args.loss, bool(info["unit_weights"]), driver.startswith("native"))
-        rate_as_built = comp_bytes / t_lin / 1e9
-        rate_counter = (traffic / t_lin / 1e9) if traffic else None
-        # `bound`: the roofline the kernel is priced against -- HBM (it streams observations; no matrix-core work).  `limiter`: what
-        # actually holds it below that roof.  The kernel moves `compulsory_bytes_as_built` (the counters agree to a few %); when that
-        # rate is below half the HBM peak the memory system is not the limit: round 6 measured the floor (profiles/r6_linearize_floor.txt:
-        # LDS atomics compiled out -3 %, all camera-sum work out -19 %, deeper prefetch nothing) -- vector issue at four waves per SIMD
-        # with the LDS pipe beside it.  (Rounds 3-5 wrote "lds" into `bound`.)
-        bound = "hbm"
-        limiter = "hbm" if (rate_counter if rate_counter is not None else rate_as_built) >= 0.5 * HBM_PEAK_GBPS else "vector issue + LDS pipe at 4 waves/SIMD"
         out = {
             "metric": "LM iters/sec at 200 cams x 1M pts x 10M obs (affine, R+T)" if args.shape == "C4" else
                       "LM iters/sec, config {}".format(args.shape),
@@ -474,27 +493,49 @@ def main():
                        .format(args.shape, n_cam, n_pts, p.n_obs, model, "+".join(corr)),
                        "sharding": "points over {} rank(s)".format(world),
                        "obs_per_rank0": K_loc},
-            "obs_per_sec_residual_jacobian": world * K_loc / t_lin,
-            # achieved / frac: SURVEY 8d's algorithmic bytes (48 K + 96 N: a throughput-equivalent, the kernel no longer moves all
-            # of them); *_as_built: the bytes this kernel has to move; achieved_counter: the bytes the PMC counters saw it move
-            # (bound and the as-built fraction first: `frac` is the throughput equivalent and must not be read without them)
-            "roofline": {"bound": bound, "limiter": limiter, "frac_as_built": rate_as_built / HBM_PEAK_GBPS,
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "achieved_counter": rate_counter,
-                         "compulsory_bytes_as_built": comp_bytes, "achieved_as_built": rate_as_built,
-                         "kernel": "k_linearize",
-                         "algorithmic_bytes_per_launch": alg_bytes, "ms_per_launch": 1e3 * t_lin, "launches_timed": n_lin,
-                         "ms_per_launch_back_to_back": kern["linearize"]},
-            "kernel_ms": kern,
-            # several ranks: device time per phase and collective, host time in blocking header reads (per iteration).  Taken in a separate
-            # pass with the PYTHON host loop (lm_step: torch events around every phase, two blocking header reads per iteration) -- the
-            # timed figure above comes from `host_driver`, which for "device" has no host wait at all: host_wait below is that pass's
-            "phase_ms": phase_ms, "phase_ms_driver": "python" if phase_ms is not None else None,
+        }
+        if full:
+            alg_bytes = 48.0 * K_loc + 96.0 * N_loc
+            # the roofline kernel's duration: average over its launches INSIDE the timed LM iterations (HIP events on the launch
+            # stream); kernel_ms["linearize"] is the same kernel in 20 back-to-back launches after the loop (a few % slower: the loop
+            # leaves part of the working set in the Infinity Cache)
+            t_lin = (ms_lin / n_lin if n_lin else kern["linearize"]) * 1e-3
+            achieved = alg_bytes / t_lin / 1e9
+            traffic = profiled_traffic(args.shape, args.loss, world)
+            comp_bytes = compulsory_bytes(K_loc, N_loc, model, p.n_params, args.loss, bool(info["unit_weights"]), driver.startswith("native"))
+            rate_as_built = comp_bytes / t_lin / 1e9
+            rate_counter = (traffic / t_lin / 1e9) if traffic else None
+            # `bound`: the roofline the kernel is priced against -- HBM (it streams observations; no matrix-core work).  `limiter`: what
+            # actually holds it below that roof.  The kernel moves `compulsory_bytes_as_built` (the counters agree to a few %); when that
+            # rate is below half the HBM peak the memory system is not the limit: round 6 measured the floor (profiles/r6_linearize_floor.txt:
+            # LDS atomics compiled out -3 %, all camera-sum work out -19 %, deeper prefetch nothing) -- vector issue at four waves per SIMD
+            # with the LDS pipe beside it.  (Rounds 3-5 wrote "lds" into `bound`.)
+            bound = "hbm"
+            limiter = "hbm" if (rate_counter if rate_counter is not None else rate_as_built) >= 0.5 * HBM_PEAK_GBPS else "vector issue + LDS pipe at 4 waves/SIMD"
+            out.update({
+                "obs_per_sec_residual_jacobian": world * K_loc / t_lin,
+                # achieved / frac: SURVEY 8d's algorithmic bytes (48 K + 96 N: a throughput-equivalent, the kernel no longer moves all
+                # of them); *_as_built: the bytes this kernel has to move; achieved_counter: the bytes the PMC counters saw it move
+                # (bound and the as-built fraction first: `frac` is the throughput equivalent and must not be read without them)
+                "roofline": {"bound": bound, "limiter": limiter, "frac_as_built": rate_as_built / HBM_PEAK_GBPS,
+                             "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                             "achieved_counter": rate_counter,
+                             "compulsory_bytes_as_built": comp_bytes, "achieved_as_built": rate_as_built,
+                             "kernel": "k_linearize",
+                             "algorithmic_bytes_per_launch": alg_bytes, "ms_per_launch": 1e3 * t_lin, "launches_timed": n_lin,
+                             "ms_per_launch_back_to_back": kern["linearize"]},
+                "kernel_ms": kern,
+                # several ranks: device time per phase and collective, host time in blocking header reads (per iteration).  Taken in a separate
+                # pass with the PYTHON host loop (lm_step: torch events around every phase, two blocking header reads per iteration) -- the
+                # timed figure above comes from `host_driver`, which for "device" has no host wait at all: host_wait below is that pass's
+                "phase_ms": phase_ms, "phase_ms_driver": "python" if phase_ms is not None else None,
+            })
+        out.update({
             "accepted_steps": st["accepted"], "interior_2d_steps": st.get("interior", 0), "final_cost": st["cost"], "scene_gen_s": t_gen,
             "launch_patterns_executed": int(ls["ticks"]) if ls else None,  # > steps when a factorisation had to be repeated with more damping
-        }
-        if world == 1 and not args.no_e2e:
+        })
+        if full and world == 1 and not args.no_e2e:
             # The drop-in call a user of the reference makes: ba_core.run_ba_optimization(p, ls_params) (ref:bundle_adjust/ba_core.py:244-332;
             # the reference times the solve inside it at :283-299).  Wall clock of the first call -- engine creation: upload of the four
             # observation arrays, layout construction on the device -- and of a warm one (cached engine), split into its parts; the
@@ -515,7 +556,7 @@ def main():
                 tm["host_overhead_frac"] = 1.0 - tm["solve_s"] / tm["wall_s"]
                 e2e[which] = tm
             out["e2e"] = e2e
-        if args.cpu_sample_pts > 0 and world == 1:
+        if full and args.cpu_sample_pts > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(scene, min(args.cpu_sample_pts, n_pts), corr, full_c3=args.cpu_c3)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out))

@@ -496,7 +496,8 @@ def test_pipeline_shaped_driver_through_dropin_names(gpu, tmp_path):
 
 @pytest.mark.parametrize("driver", ["native", "python"])
 def test_bench_line_contract(gpu, driver):
-    """bench.py on the small shape, as a child process: one JSON line with the keys the driver's contract names, both host drivers."""
+    """bench.py --full on the small shape, as a child process: one JSON line with the keys the driver's contract names, both host
+    drivers."""
     import json
     import os
     import subprocess
@@ -504,13 +505,13 @@ def test_bench_line_contract(gpu, driver):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--shape", "C2", "--steps", "8", "--warmup", "2", "--cpu-sample-pts", "0",
-                          "--driver", driver], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--driver", driver, "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-              "data", "config", "roofline", "restart_every"):  # cpu_baseline: the default run's extra leg, skipped here (--cpu-sample-pts 0)
+              "data", "config", "roofline", "restart_every"):  # cpu_baseline: an extra leg of --full, skipped here (--cpu-sample-pts 0)
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["dtype"] == "f64" and d["vs_baseline"] is None
     assert d["unit"] == "LM iters/sec" and d["higher_is_better"] is True and "workload" in d["config"]
@@ -525,10 +526,43 @@ def test_bench_line_contract(gpu, driver):
     assert d["accepted_steps"] >= 4  # restarts keep the timed steps productive
 
 
+def test_bench_plain_line_and_outputs(gpu, tmp_path):
+    """A plain bench.py run (no --full): the headline keys and nothing of the extra passes; --dump-outputs writes the point, cost and
+    radius after the last timed step, and two runs with the same arguments write the same bits."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--shape", "C2", "--steps", "8", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "final_cost"):
+            assert key in d, key
+        for key in ("roofline", "kernel_ms", "phase_ms", "e2e", "cpu_baseline"):
+            assert key not in d, key
+        assert d["steps"] == 8 and d["warmup"] == 2 and d["dtype"] == "f64" and d["unit"] == "LM iters/sec" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        a = {n: np.load(tmp_path / str(k) / (n + ".npy")) for n in ("x_cameras", "x_points", "cost", "trust_radius")}
+        assert all(v.dtype == np.float64 for v in a.values())
+        assert a["x_cameras"].shape[0] == 10 and a["x_points"].shape == (5000, 3) and a["cost"][0] == d["final_cost"]
+        assert np.isfinite(a["x_points"]).all() and a["trust_radius"][0] > 0.0
+        runs.append(a)
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+
+
 @pytest.mark.parametrize("driver", ["device", "python"])
-def test_bench_line_two_ranks(gpu, driver):
+def test_bench_line_two_ranks(gpu, tmp_path, driver):
     """bench.py --gpus 2 the way the scaling runs launch it (torch.distributed.run, one process per rank), on this one GPU over gloo
-    (--backend gloo --share-gpu: test switches): the line of rank 0, whole-job value, the per-phase breakdown, both host drivers."""
+    (--backend gloo --share-gpu: test switches): the line of rank 0, whole-job value, the per-phase breakdown (--full), both host
+    drivers."""
     import json
     import os
     import socket
@@ -541,7 +575,7 @@ def test_bench_line_two_ranks(gpu, driver):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--shape", "C2", "--steps", "8", "--warmup", "2", "--cpu-sample-pts", "0",
-           "--backend", "gloo", "--share-gpu", "--driver", driver]
+           "--backend", "gloo", "--share-gpu", "--driver", driver, "--full", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -553,3 +587,5 @@ def test_bench_line_two_ranks(gpu, driver):
     for k in ("linearize", "prepare", "schur", "dense_solve", "trial", "allreduce", "allreduce_schur", "host_wait"):
         assert k in ph and ph[k] >= 0.0, k
     assert d["accepted_steps"] >= 4 and d["config"]["obs_per_rank0"] < 29981  # a shard, not the whole scene
+    # the outputs are the whole point: both ranks' points gathered
+    assert np.load(tmp_path / "x_points.npy").shape == (5000, 3) and np.load(tmp_path / "cost.npy")[0] == d["final_cost"]

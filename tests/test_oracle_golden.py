@@ -2,7 +2,6 @@
 Pins the CPU oracle (oracle/) and the host-side packing code (satba.ba_params, satba.cam_utils, satba.ba_rotate)
 on vectors captured from the reference itself by tools/gen_golden.py.  No GPU.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -130,37 +129,17 @@ def test_reference_forward_differences_displace_its_own_minimum(name, loss):
 
 
 def test_rpc_projection_against_reference_c():
-    """oracle.rpc_projection and satba.RPCModel.projection vs the reference's own C evaluator (ref:c/rpc.c:442-452)."""
-    lib_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "librpc.so")
-    if not os.path.exists(lib_path):
-        pytest.skip("oracle/_ref/librpc.so not built (needs /root/reference; run `make -C oracle`)")
-    lib = ctypes.CDLL(lib_path)
-
-    class Rpc(ctypes.Structure):  # struct rpc of ref:c/rpc.h:14-32
-        _fields_ = [(n, ctypes.c_double * k) for n, k in (
-            ("numx", 20), ("denx", 20), ("numy", 20), ("deny", 20), ("scale", 3), ("offset", 3), ("inumx", 20),
-            ("idenx", 20), ("inumy", 20), ("ideny", 20), ("iscale", 3), ("ioffset", 3), ("dmval", 4), ("imval", 4))] + [
-            ("delta", ctypes.c_double)]
-
-    lib.eval_rpci.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(Rpc)] + [ctypes.c_double] * 3
-    rng = np.random.default_rng(0)
-    for path in synth.default_rpc_files():
+    """oracle.rpc_projection and satba.RPCModel.projection vs the reference's own C evaluator (ref:c/rpc.c:442-452): its outputs on 50
+    random points per shipped RPC, stored by tools/gen_golden.py reference_c."""
+    g = cases.golden("reference_c")
+    for k, path in enumerate(synth.default_rpc_files()):
         r = RPCModel.from_file(path)
-        s = Rpc()  # attribute <-> struct mapping of ref:bundle_adjust/s2p/triangulation.py:43-61
-        s.inumx[:], s.idenx[:], s.inumy[:], s.ideny[:] = r.col_num, r.col_den, r.row_num, r.row_den
-        s.ioffset[:] = [r.lon_offset, r.lat_offset, r.alt_offset]
-        s.iscale[:] = [r.lon_scale, r.lat_scale, r.alt_scale]
-        s.offset[:] = [r.col_offset, r.row_offset, r.alt_offset]
-        s.scale[:] = [r.col_scale, r.row_scale, r.alt_scale]
-        lon = r.lon_offset + rng.uniform(-0.02, 0.02, 50)
-        lat = r.lat_offset + rng.uniform(-0.02, 0.02, 50)
-        alt = r.alt_offset + rng.uniform(-500, 500, 50)
+        lon, lat, alt = g["proj%d_lonlatalt" % k].T
         col, row = O.rpc_projection(r, lon, lat, alt)
         col2, row2 = r.projection(lon, lat, alt)
-        out = (ctypes.c_double * 2)()
-        for i in range(50):
-            lib.eval_rpci(out, ctypes.byref(s), lon[i], lat[i], alt[i])
-            assert abs(out[0] - col[i]) < 1e-9 and abs(out[1] - row[i]) < 1e-9
+        out = g["proj%d_colrow" % k]
+        assert out.shape == (50, 2)
+        assert np.abs(out[:, 0] - col).max() < 1e-9 and np.abs(out[:, 1] - row).max() < 1e-9
         assert np.abs(col - col2).max() < 1e-9 and np.abs(row - row2).max() < 1e-9
 
 
@@ -269,47 +248,18 @@ def test_triangulation_oracle_reproduces_reference(name):
 
 
 def test_rpc_triangulation_oracle_against_reference_c():
-    """oracle.stereo_corresp_to_lonlatalt vs the reference's own library (ref:c/disp_to_h.c:40-64, built by oracle/Makefile)."""
+    """oracle.stereo_corresp_to_lonlatalt vs the reference's own library (ref:c/disp_to_h.c:40-64, built by oracle/Makefile): its outputs
+    on 500 noisy correspondences, stored by tools/gen_golden.py reference_c."""
     from oracle import triangulate_oracle as T
 
-    lib_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "disp_to_h.so")
-    if not os.path.exists(lib_path):
-        pytest.skip("oracle/_ref/disp_to_h.so not built (needs /root/reference; run `make -C oracle`)")
-    lib = ctypes.CDLL(lib_path)
-
-    class Rpc(ctypes.Structure):  # struct rpc of ref:c/rpc.h:14-32
-        _fields_ = [(n, ctypes.c_double * k) for n, k in (
-            ("numx", 20), ("denx", 20), ("numy", 20), ("deny", 20), ("scale", 3), ("offset", 3), ("inumx", 20),
-            ("idenx", 20), ("inumy", 20), ("ideny", 20), ("iscale", 3), ("ioffset", 3), ("dmval", 4), ("imval", 4))] + [
-            ("delta", ctypes.c_double)]
-
-    def fill(r):  # ref:bundle_adjust/s2p/triangulation.py:43-79 with delta = 0.1 (:99-100)
-        s = Rpc()
-        s.inumx[:], s.idenx[:], s.inumy[:], s.ideny[:] = r.col_num, r.col_den, r.row_num, r.row_den
-        s.numx[:] = s.denx[:] = s.numy[:] = s.deny[:] = [float("nan")] * 20
-        s.ioffset[:] = [r.lon_offset, r.lat_offset, r.alt_offset]
-        s.iscale[:] = [r.lon_scale, r.lat_scale, r.alt_scale]
-        s.offset[:] = [r.col_offset, r.row_offset, r.alt_offset]
-        s.scale[:] = [r.col_scale, r.row_scale, r.alt_scale]
-        s.delta = 0.1
-        return s
-
+    g = cases.golden("reference_c")
     r1, r2 = [RPCModel.from_file(f) for f in synth.default_rpc_files()]
-    rng = np.random.default_rng(3)
-    n = 500
-    lon = r1.lon_offset + rng.uniform(-0.01, 0.01, n); lat = r1.lat_offset + rng.uniform(-0.005, 0.005, n)
-    alt = r1.alt_offset + rng.uniform(-100, 100, n)
-    p1 = np.stack(r1.projection(lon, lat, alt), 1) + rng.normal(0, 0.2, (n, 2))
-    p2 = np.stack(r2.projection(lon, lat, alt), 1) + rng.normal(0, 0.2, (n, 2))
-    out = np.zeros((n, 3)); err = np.zeros((n, 1), np.float32)
-    a32, b32 = np.ascontiguousarray(p1.astype(np.float32)), np.ascontiguousarray(p2.astype(np.float32))
-    vp = ctypes.c_void_p
-    lib.stereo_corresp_to_lonlatalt(out.ctypes.data_as(vp), err.ctypes.data_as(vp), a32.ctypes.data_as(vp), b32.ctypes.data_as(vp),
-                                    ctypes.c_int(n), ctypes.byref(fill(r1)), ctypes.byref(fill(r2)))
-    lla, e = T.stereo_corresp_to_lonlatalt(r1, r2, p1, p2)
+    out, err, alt = g["tri_lonlatalt"], g["tri_err"], g["tri_alt"]
+    assert out.shape == (500, 3)
+    lla, e = T.stereo_corresp_to_lonlatalt(r1, r2, g["tri_p1"], g["tri_p2"])
     # same sequence of IEEE operations; a compiler that contracts a*b+c differently would still agree to these bounds
     assert np.abs(lla[:, :2] - out[:, :2]).max() < 1e-12 and np.abs(lla[:, 2] - out[:, 2]).max() < 1e-6
-    assert np.abs(e - err[:, 0]).max() < 1e-6
+    assert np.abs(e - err).max() < 1e-6
     assert np.abs(out[:, 2] - alt).max() < 5.0  # and the library triangulates the scene it was given
 
 

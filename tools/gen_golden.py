@@ -529,9 +529,68 @@ def golden_rpcfit():
     save("rpcfit", **out)
 
 
+def golden_reference_c():
+    """
+    The reference's own C on the two shipped RPCs, built by oracle/Makefile into oracle/_ref/: ref:c/rpc.c:442-452 eval_rpci (projection,
+    50 random points per RPC) and ref:c/disp_to_h.c:40-64 stereo_corresp_to_lonlatalt (500 noisy correspondences; float32 image points,
+    delta 0.1 as ref:bundle_adjust/s2p/triangulation.py:99-100 passes it).  The tests compare the oracle against these outputs.
+    """
+    import ctypes
+    from satba.rpc_model import RPCModel
+
+    class Rpc(ctypes.Structure):  # struct rpc of ref:c/rpc.h:14-32
+        _fields_ = [(n, ctypes.c_double * k) for n, k in (
+            ("numx", 20), ("denx", 20), ("numy", 20), ("deny", 20), ("scale", 3), ("offset", 3), ("inumx", 20),
+            ("idenx", 20), ("inumy", 20), ("ideny", 20), ("iscale", 3), ("ioffset", 3), ("dmval", 4), ("imval", 4))] + [
+            ("delta", ctypes.c_double)]
+
+    def fill(r):  # attribute <-> struct mapping of ref:bundle_adjust/s2p/triangulation.py:43-79
+        s = Rpc()
+        s.inumx[:], s.idenx[:], s.inumy[:], s.ideny[:] = r.col_num, r.col_den, r.row_num, r.row_den
+        s.numx[:] = s.denx[:] = s.numy[:] = s.deny[:] = [float("nan")] * 20
+        s.ioffset[:] = [r.lon_offset, r.lat_offset, r.alt_offset]
+        s.iscale[:] = [r.lon_scale, r.lat_scale, r.alt_scale]
+        s.offset[:] = [r.col_offset, r.row_offset, r.alt_offset]
+        s.scale[:] = [r.col_scale, r.row_scale, r.alt_scale]
+        s.delta = 0.1
+        return s
+
+    rpcs = [RPCModel.from_file(f) for f in synth.default_rpc_files()]
+    out = {}
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "librpc.so"))
+    lib.eval_rpci.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(Rpc)] + [ctypes.c_double] * 3
+    rng = np.random.default_rng(0)
+    for k, r in enumerate(rpcs):
+        s = fill(r)
+        lon = r.lon_offset + rng.uniform(-0.02, 0.02, 50)
+        lat = r.lat_offset + rng.uniform(-0.02, 0.02, 50)
+        alt = r.alt_offset + rng.uniform(-500, 500, 50)
+        cr = np.zeros((50, 2))
+        res = (ctypes.c_double * 2)()
+        for i in range(50):
+            lib.eval_rpci(res, ctypes.byref(s), lon[i], lat[i], alt[i])
+            cr[i] = res[0], res[1]
+        out.update({"proj%d_lonlatalt" % k: np.stack([lon, lat, alt], 1), "proj%d_colrow" % k: cr})
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "disp_to_h.so"))
+    r1, r2 = rpcs
+    rng = np.random.default_rng(3)
+    n = 500
+    lon = r1.lon_offset + rng.uniform(-0.01, 0.01, n); lat = r1.lat_offset + rng.uniform(-0.005, 0.005, n)
+    alt = r1.alt_offset + rng.uniform(-100, 100, n)
+    p1 = np.stack(r1.projection(lon, lat, alt), 1) + rng.normal(0, 0.2, (n, 2))
+    p2 = np.stack(r2.projection(lon, lat, alt), 1) + rng.normal(0, 0.2, (n, 2))
+    lla = np.zeros((n, 3)); err = np.zeros((n, 1), np.float32)
+    a32, b32 = np.ascontiguousarray(p1.astype(np.float32)), np.ascontiguousarray(p2.astype(np.float32))
+    vp = ctypes.c_void_p
+    lib.stereo_corresp_to_lonlatalt(lla.ctypes.data_as(vp), err.ctypes.data_as(vp), a32.ctypes.data_as(vp), b32.ctypes.data_as(vp),
+                                    ctypes.c_int(n), ctypes.byref(fill(r1)), ctypes.byref(fill(r2)))
+    out.update({"tri_alt": alt, "tri_p1": p1, "tri_p2": p2, "tri_lonlatalt": lla, "tri_err": err[:, 0]})
+    save("reference_c", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["fun", "params", "solves", "solves4", "tight2", "tight3", "outliers", "init_pts3d", "rpcfit"]
+    which = sys.argv[1:] or ["fun", "params", "solves", "solves4", "tight2", "tight3", "outliers", "init_pts3d", "rpcfit", "reference_c"]
     if "fun" in which:
         golden_fun_and_jac()
     if "params" in which:
@@ -550,3 +609,5 @@ if __name__ == "__main__":
         golden_init_pts3d()
     if "rpcfit" in which:
         golden_rpcfit()
+    if "reference_c" in which:
+        golden_reference_c()

@@ -1,15 +1,16 @@
 #!/bin/bash
 # Runs ON the GPU box (through gpurun): the evidence runs of a round, one sub-command each.  Everything lands in gpurun_out/TAG/.
 #   tools/gpu.sh TAG tests                       pytest -m gpu + smoke()
-#   tools/gpu.sh TAG bench [bench.py args]       python bench.py ... -> bench.json  (repeat with other args / tags for other shapes)
-#   tools/gpu.sh TAG benches                     the bench lines of every shape and loss (C4, C2, C3, P3, C5; linear and soft_l1)
-#   tools/gpu.sh TAG stats [bench.py args]       rocprofv3 --kernel-trace --stats over bench.py (no CPU leg) -> kernel_stats.txt
+#   tools/gpu.sh TAG bench [bench.py args]       python bench.py --full ... -> bench.json  (repeat with other args / tags for other shapes)
+#   tools/gpu.sh TAG benches                     the --full bench lines of every shape and loss (C4, C2, C3, P3, C5; linear and soft_l1)
+#   tools/gpu.sh TAG stats [bench.py args]       rocprofv3 --kernel-trace --stats over bench.py --full (no CPU leg) -> kernel_stats.txt
 #   tools/gpu.sh TAG pmc SHAPE LOSS REGEX        PMC passes (separate runs, counters only) over tools/kernel_times.py -> pmc_summary.txt
 #   tools/gpu.sh TAG pmc_loop SHAPE LOSS         FETCH_SIZE / WRITE_SIZE of the kernels inside LM iterations -> pmc_summary.txt
 #   tools/gpu.sh TAG chol N...                   tools/chol/chol_bench (dense solve harness) at the given sizes
 #   tools/gpu.sh TAG calib                       tools/ubench/fetch_calib.bin: FETCH_SIZE / request counters against known byte counts
 # (rounds 1-3 had one script per experiment: tools/gpu_*.sh, 21 of them)
 tag=$1; cmd=$2; shift 2
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
@@ -27,18 +28,18 @@ tests)
   grep -E "passed|failed|rror" $out/pytest_gpu.log | tail -3
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log ;;
 bench)
-  timeout 900 python bench.py "$@" > $out/bench.json 2> $out/bench.err; summ $out/bench.json ;;
+  timeout 900 python bench.py --full "$@" > $out/bench.json 2> $out/bench.err; summ $out/bench.json ;;
 benches)
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
-  timeout 300 python bench.py --loss soft_l1 --cpu-sample-pts 0 > $out/bench_soft_l1.json 2>> $out/bench.err
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
+  timeout 300 python bench.py --full --loss soft_l1 --cpu-sample-pts 0 > $out/bench_soft_l1.json 2>> $out/bench.err
   for s in C2 C3 P3 C5; do
-    timeout 300 python bench.py --shape $s --cpu-sample-pts 0 > $out/bench_$s.json 2>> $out/bench.err
-    timeout 300 python bench.py --shape $s --loss soft_l1 --cpu-sample-pts 0 > $out/bench_${s}_soft_l1.json 2>> $out/bench.err
+    timeout 300 python bench.py --full --shape $s --cpu-sample-pts 0 > $out/bench_$s.json 2>> $out/bench.err
+    timeout 300 python bench.py --full --shape $s --loss soft_l1 --cpu-sample-pts 0 > $out/bench_${s}_soft_l1.json 2>> $out/bench.err
   done
   summ $out/bench*.json ;;
 stats)
   cd /tmp && export TMPDIR=/tmp
-  timeout 600 rocprofv3 --kernel-trace --stats -d $out/prof -o stats -- python3 $GRAFT_REPO_ROOT/bench.py --cpu-sample-pts 0 "$@" > $out/bench_profiled.json 2> $out/prof.log
+  timeout 600 rocprofv3 --kernel-trace --stats -d $out/prof -o stats -- python3 $root/bench.py --full --cpu-sample-pts 0 "$@" > $out/bench_profiled.json 2> $out/prof.log
   python3 $GRAFT_REPO_ROOT/tools/rocpd_stats.py $out/prof/stats_results.db > $out/kernel_stats.txt
   python3 $GRAFT_REPO_ROOT/tools/rocpd_timeline.py $out/prof/stats_results.db > $out/timeline.txt 2>&1
   head -${HEAD_LINES:-34} $out/kernel_stats.txt; cat $out/timeline.txt
