@@ -17,6 +17,8 @@
  *     mirrors ba_core.py:150.
  *
  * Variable vector (ba_params.py:152-172):  x = [cam 0 (n_params) | ... | cam M-1 | pt 0 (3) | ... | pt N-1 (3)]
+ *   a camera's n_params entries are the first n_params of its cam_params row: angles (3), then T, then the intrinsics
+ *   (affine fx fy skew, perspective fx fy skew cx cy; n_params 8 / 11 -- satba_version() >= 4)
  * Residual vector (ba_core.py:180-181):   r = [x0, y0, x1, y1, ...] = w_k * (projection_k - observation_k)
  *
  * Multi-GPU: one process and one handle per GPU.  Each handle holds ALL cameras and a contiguous shard of the
@@ -76,7 +78,8 @@ typedef struct satba_problem_desc {
     int32_t cam_model;      /* SATBA_AFFINE | SATBA_PERSPECTIVE | SATBA_RPC  (BundleAdjustmentParameters.cam_model) */
     int32_t n_cam;          /* M                                                                    */
     int32_t n_pts;          /* N: points held by this handle                                        */
-    int32_t n_params;       /* optimised parameters per camera: 3 (R) | 5 (affine R+T) | 6 (R+T)     */
+    int32_t n_params;       /* optimised parameters per camera: 3 (R) | 5 (affine R+T) | 6 (R+T) |
+                               8 (affine R+T+K) | 11 (perspective R+T+K)                              */
     int32_t cam_param_len;  /* columns of cam_params: 8 affine, 11 perspective, 9 rpc (ba_params.py:19-44) */
     int32_t n_cam_fix;      /* first n_cam_fix cameras are frozen (ba_params.py:246-249)             */
     int32_t n_pts_fix;      /* first n_pts_fix LOCAL points are frozen (ba_params.py:240-243)        */

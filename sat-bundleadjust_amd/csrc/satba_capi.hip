@@ -216,8 +216,8 @@ static int dev_alloc(satba_problem* p, T** out, size_t count) {
         if (rc_) return rc_; \
     } while (0)
 
-// dispatch on (camera model, parameters per camera, camera table in LDS, RPC table in LDS); valid pairs: affine {3,5},
-// perspective / rpc {3,6}
+// dispatch on (camera model, parameters per camera, camera table in LDS, RPC table in LDS); valid pairs: affine {3,5,8},
+// perspective {3,6,11}, rpc {3,6}
 #define SATBA_CASE(key, M_, NP_, CL_, RL_, ...)                                                                    \
     case key: { constexpr int MODEL = M_, NP = NP_; constexpr bool CL = CL_, RL = RL_; (void)CL; (void)RL; __VA_ARGS__; } break;
 #define SATBA_DISPATCH(p, ...)                                                                                    \
@@ -240,6 +240,10 @@ static int dev_alloc(satba_problem* p, T** out, size_t count) {
             SATBA_CASE(1126, RPC, 6, true, true, __VA_ARGS__)                                                     \
             SATBA_CASE(1023, RPC, 3, false, true, __VA_ARGS__)                                                    \
             SATBA_CASE(1026, RPC, 6, false, true, __VA_ARGS__)                                                    \
+            SATBA_CASE(8, AFFINE, 8, false, false, __VA_ARGS__)                                                   \
+            SATBA_CASE(21, PERSPECTIVE, 11, false, false, __VA_ARGS__)                                            \
+            SATBA_CASE(108, AFFINE, 8, true, false, __VA_ARGS__)                                                  \
+            SATBA_CASE(121, PERSPECTIVE, 11, true, false, __VA_ARGS__)                                            \
             default: return fail(SATBA_E_ARG, "unsupported (cam_model, n_params) = (%d, %d)", (p)->model, (p)->NP);           \
         }                                                                                                         \
     } while (0)
@@ -399,18 +403,18 @@ static int launch_lin(satba_problem* p, const ObsArgs& a) {
     double* gmax = p->d_xb + SATBA_HDR_FIXED + p->rank;
     const size_t lds = lin_lds(p);
     const RedBuf rb = p->red(RB_LIN);
-    constexpr bool BIGL = MODEL == RPC;  // LinCfg of the linear-loss variants
+    constexpr bool BIGL = MODEL == RPC || NP > 6;  // LinCfg of the linear-loss variants (k_linearize's own choice)
 #define SATBA_LIN_LAUNCH(ROB, SOFT_, UNIT_, CS_, BIG_)                                                                                   \
     hipLaunchKernelGGL((k_linearize<MODEL, NP, ROB, CL, RL, SOFT_, UNIT_, CS_>), dim3(p->lin_grid), dim3(LinCfg<BIG_>::THREADS), lds, p->stream, \
                        a, (p->cam_sums_lds || MODEL != RPC) ? nullptr : p->d_f, p->d_V, gpv, p->d_part, rb, cost, gmax)
     const int v = lin_variant(p);
     if (p->cam_sums_lds) {
-        if (v == 0) { if constexpr (MODEL != RPC) SATBA_LIN_LAUNCH(false, false, true, true, false); }
+        if (v == 0) { if constexpr (MODEL != RPC) SATBA_LIN_LAUNCH(false, false, true, true, BIGL); }
         else if (v == 1) SATBA_LIN_LAUNCH(false, false, false, true, BIGL);
         else if (v == 2) SATBA_LIN_LAUNCH(true, true, false, true, BIGL);
         else SATBA_LIN_LAUNCH(true, false, false, true, true);
     } else {
-        if (v == 0) { if constexpr (MODEL != RPC) SATBA_LIN_LAUNCH(false, false, true, false, false); }
+        if (v == 0) { if constexpr (MODEL != RPC) SATBA_LIN_LAUNCH(false, false, true, false, BIGL); }
         else if (v == 1) SATBA_LIN_LAUNCH(false, false, false, false, BIGL);
         else if (v == 2) SATBA_LIN_LAUNCH(true, true, false, false, BIGL);
         else SATBA_LIN_LAUNCH(true, false, false, false, true);
@@ -981,7 +985,7 @@ static int build_layout(satba_problem* p, const satba_problem_desc* d) {
 extern "C" {
 
 const char* satba_last_error(void) { return g_err.c_str(); }
-int satba_version(void) { return 3; }
+int satba_version(void) { return 4; }
 
 int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
     Range range_("satba:problem_create");
@@ -991,7 +995,11 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
     const int c_p_expected = d->cam_model == SATBA_AFFINE ? 8 : (d->cam_model == SATBA_PERSPECTIVE ? 11 : 9);
     if (d->cam_param_len != c_p_expected) return fail(SATBA_E_ARG, "cam_param_len %d, expected %d", d->cam_param_len, c_p_expected);
     const int np_rt = d->cam_model == SATBA_AFFINE ? 5 : 6;
-    if (d->n_params != 3 && d->n_params != np_rt) return fail(SATBA_E_ARG, "n_params %d not in {3, %d}", d->n_params, np_rt);
+    const int np_rtk = d->cam_model == SATBA_AFFINE ? 8 : (d->cam_model == SATBA_PERSPECTIVE ? 11 : 0);  // + intrinsics (not rpc)
+    if (d->n_params != 3 && d->n_params != np_rt && (np_rtk == 0 || d->n_params != np_rtk)) {
+        if (np_rtk) return fail(SATBA_E_ARG, "n_params %d not in {3, %d, %d}", d->n_params, np_rt, np_rtk);
+        return fail(SATBA_E_ARG, "n_params %d not in {3, %d}", d->n_params, np_rt);
+    }
     if (d->n_cam <= 0 || d->n_pts < 0 || d->n_obs < 0) return fail(SATBA_E_ARG, "negative size");
     if (d->n_obs >= (1ll << 31) - 64) return fail(SATBA_E_ARG, "more than 2^31 observations per shard");
     if (!d->cam_params || (d->n_obs && (!d->cam_ind || !d->pts_ind || !d->pts2d || !d->weights)))
@@ -1069,7 +1077,8 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
             HIP_TRY(hipMemset(p->chol.ctr, 0, sizeof(int) * 4));
         }
         TRY(dev_alloc(p, &p->d_scal, 8));
-        TRY(dev_alloc(p, &p->d_fx, 2 * 6)); TRY(dev_alloc(p, &p->d_fxe, 6 + 4)); TRY(dev_alloc(p, &p->d_bbox, 6)); TRY(dev_alloc(p, &p->d_fxflag, 1));
+        TRY(dev_alloc(p, &p->d_fx, fx_scales_len(p->NP))); TRY(dev_alloc(p, &p->d_fxe, fx_exps_len(p->NP)));  // (sized by NP: 8 and 11 need more than 6)
+        TRY(dev_alloc(p, &p->d_bbox, 6)); TRY(dev_alloc(p, &p->d_fxflag, 1));
         TRY(dev_alloc(p, &p->d_fxcost, 1)); TRY(dev_alloc(p, &p->d_fxcost_new, 1)); TRY(dev_alloc(p, &p->d_fxcost0, 1));
         HIP_TRY(hipMemset(p->d_bbox, 0, sizeof(double) * 6));
         HIP_TRY(hipMemset(p->d_fxflag, 0, sizeof(int)));

@@ -40,6 +40,10 @@ constexpr int FX_LO_SHIFT = 40;  // the low limb of a g_c term holds its remaind
 constexpr long long FX_MAX_OBS_PER_CAM = 1ll << 23;
 // (a multiple of 16 bytes: the camera-constant rows behind the table are read with ds_read_b128)
 __host__ __device__ constexpr size_t cam_sum_bytes(int np, size_t rows) { return (rows * cam_sum_stride(np) * 8 + 15) & ~(size_t)15; }
+// the fixed-point scales of the camera sums (k_lin_scales, k_lm_accept_scales write them; k_linearize, k_lin_finish read them):
+// fx = 2 np inverse scales, fxe = np + 1 exponents and the two range-check constants
+__host__ __device__ constexpr int fx_scales_len(int np) { return 2 * np; }
+__host__ __device__ constexpr int fx_exps_len(int np) { return np + 3; }
 
 // row stride of the LDS copy of the RPC tables: 90 doubles used, 47 sixteen-byte slots (odd: the rows of consecutive cameras start in all
 // 16 slots of the bank row).  Round 6: with 91 doubles (8-byte alignment) the 90 reads of an evaluation were 45 ds_read2_b64 pairs -- half
@@ -580,7 +584,7 @@ struct LinCfg {
 #ifndef SATBA_LIN_THREADS
 #define SATBA_LIN_THREADS 1024
 #endif
-    static constexpr int THREADS = BIG ? 512 : SATBA_LIN_THREADS;  // the generic robust variants and the RPC chain need > 128 VGPRs
+    static constexpr int THREADS = BIG ? 512 : SATBA_LIN_THREADS;  // the generic robust variants, the RPC chain and the intrinsics need > 128 VGPRs
     static constexpr int WAVES = THREADS / 64;
 };
 
@@ -590,12 +594,12 @@ struct LinCfg {
 // is applied when the workgroup's camera table is flushed, the fixed-point mask when a point's sums are stored
 // CAMSUMS = false: the camera sums are formed by k_cam_sums instead (deterministic runs, camera tables beyond the LDS)
 template <int MODEL, int NP, bool ROBUST, bool CL, bool RL, bool SOFT, bool UNITW, bool CAMSUMS>
-__global__ __launch_bounds__(LinCfg<(ROBUST && !SOFT) || MODEL == RPC>::THREADS) void k_linearize(
+__global__ __launch_bounds__(LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6)>::THREADS) void k_linearize(
     ObsArgs a, double2* __restrict__ f, double* __restrict__ V, double* __restrict__ gp, double* __restrict__ part, RedBuf rb,
     double* __restrict__ hdr_cost, double* __restrict__ hdr_gpmax) {
     SATBA_GATE(a.gate);
     constexpr int CUS = cam_sum_stride(NP);
-    using Cfg = LinCfg<(ROBUST && !SOFT) || MODEL == RPC>;
+    using Cfg = LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6)>;  // (NP > 6: the intrinsics, 8 / 11 columns per row of Jc)
     constexpr int THREADS = Cfg::THREADS, WAVES = Cfg::WAVES;
     extern __shared__ __attribute__((aligned(16))) double s_lin[];
     unsigned long long* s_acc = reinterpret_cast<unsigned long long*>(s_lin);
@@ -817,6 +821,7 @@ __global__ __launch_bounds__(1024) void k_lin_finish(int M, int NP, int nblocks,
 // terms, scaled by 2^(2 a_k), and the g terms, scaled by 2^(a_k + b), stay below 2^Q.
 // fxe: a_0 .. a_{NP-1} | b | c1 | c2  -- the range check of k_linearize is (hi32(y) + c1) <u c2, i.e. r >> 32 in [-L, L), L = 2^(Q-32);
 // fx:  [2 NP] inverse scales 2^-(2 a_k), 2^-(a_k + b).  The bounds need not be rigorous: every term is checked.
+// (lengths of the two arrays: fx_scales_len / fx_exps_len, what the handle allocates for its NP)
 // (the body: 256 threads of one workgroup; also run by a workgroup of k_lm_accept_scales, satba_lmdev.h)
 template <int MODEL, int NP>
 __device__ __forceinline__ void lin_scales_body(int M, const double* __restrict__ camc, const double* __restrict__ rpc,
@@ -1138,8 +1143,9 @@ constexpr int JVP_THREADS = SATBA_JVP_THREADS;
 #define SATBA_CAM_PF 2
 #endif
 
-// affine cameras: J_c v_c = B_c X + b_c with B_c = sum_i v_ci D_ci, b_c = K-columns . v_cT, and J_p = A_c.  Every workgroup
-// derives the 14 constants of each camera once (three evaluations of the projector's Jacobian at the unit vectors) into an
+// affine cameras: J_c v_c = B_c X + b_c with B_c = sum_i v_ci D_ci, b_c = A v_cT, and J_p = A_c (NP = 8: the intrinsics' columns, rows
+// of R X + t, add to both).  Every workgroup derives the 14 constants of each camera once (three evaluations of the projector's Jacobian
+// at the unit vectors) into an
 // LDS table of 112-byte rows; an observation then costs seven 16-byte LDS reads and 14-18 multiply-adds instead of the Jacobian
 // evaluation.  vc: the camera part of the vector (unscaled variables), n_c doubles.
 // vs (or null): vc is in scaled variables, the direction is vc / vs (as the generic path forms it: times the reciprocal)
@@ -1159,10 +1165,21 @@ __device__ inline void affine_dir_table(const ObsArgs& a, const double* __restri
                 B[0][m] += Jc[0][i] * vi; B[1][m] += Jc[1][i] * vi;
             }
         }
+        constexpr int NT = NP < 5 ? NP : 5;  // the T columns (constant: A)
 #pragma unroll
-        for (int i = 3; i < NP; ++i) {
+        for (int i = 3; i < NT; ++i) {
             const double vi = vs ? vc[c * NP + i] * (1.0 / vs[c * NP + i]) : vc[c * NP + i];
             b[0] += Jc[0][i] * vi; b[1] += Jc[1][i] * vi;
+        }
+        if constexpr (NP == 8) {
+            // K columns: (q0, 0, q1 | 0, q1, 0) with q = rows 0, 1 of R X + t -- affine in X: rows of R into B, t into b
+            double k[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) k[i] = vs ? vc[c * NP + 5 + i] * (1.0 / vs[c * NP + 5 + i]) : vc[c * NP + 5 + i];
+#pragma unroll
+            for (int m = 0; m < 3; ++m) { B[0][m] += k[0] * cc[6 + m] + k[2] * cc[9 + m]; B[1][m] += k[1] * cc[9 + m]; }
+            b[0] += k[0] * cc[CAMX] + k[2] * cc[CAMX + 1];
+            b[1] += k[1] * cc[CAMX + 1];
         }
         double* row = tab + (size_t)c * JVP_ROW;
 #pragma unroll

@@ -253,7 +253,8 @@ __device__ inline void project_rpc_d(const double* __restrict__ cc, const double
     }
 }
 
-// One observation: projection (u, v) and, if JAC, Jc (2 x NP) w.r.t. [angles(3), T(NP-3)] and Jp (2 x 3).
+// One observation: projection (u, v) and, if JAC, Jc (2 x NP) w.r.t. [angles(3), T, K] and Jp (2 x 3): NP = 3 angles only, 5 / 6
+// angles and T (affine / perspective and rpc), 8 / 11 angles, T and the intrinsics K (affine fx fy skew, perspective fx fy skew cx cy)
 template <int MODEL, int NP, bool JAC>
 __device__ inline void project(const double* __restrict__ cc, const double* __restrict__ rpc_tab, double X, double Y,
                                double Z, bool f32, double& u, double& v, double Jc[2][NP], double Jp[2][3]) {
@@ -274,6 +275,12 @@ __device__ inline void project(const double* __restrict__ cc, const double* __re
             if constexpr (NP == 5) {  // d/dt = A
                 Jc[0][3] = fx; Jc[0][4] = sk;
                 Jc[1][3] = 0.0; Jc[1][4] = fy;
+            }
+            if constexpr (NP == 8) {  // d/dt = A; d/d(fx, fy, skew) = (q0, 0, q1) | (0, q1, 0)
+                Jc[0][3] = fx; Jc[0][4] = sk;
+                Jc[1][3] = 0.0; Jc[1][4] = fy;
+                Jc[0][5] = q0; Jc[0][6] = 0.0; Jc[0][7] = q1;
+                Jc[1][5] = 0.0; Jc[1][6] = q1; Jc[1][7] = 0.0;
             }
             // rows 0 and 1 of R from the six trig values already in registers (same expressions as cam_constants):
             // six fewer gathers from the LDS camera table per observation; the kernels are bound by the LDS pipe
@@ -303,12 +310,17 @@ __device__ inline void project(const double* __restrict__ cc, const double* __re
                 Jc[0][i] = D[0][0] * d[i][0] + D[0][1] * d[i][1] + D[0][2] * d[i][2];
                 Jc[1][i] = D[1][1] * d[i][1] + D[1][2] * d[i][2];
             }
-            if constexpr (NP == 6) {  // d/dt = D
+            if constexpr (NP == 6 || NP == 11) {  // d/dt = D
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     Jc[0][3 + j] = D[0][j];
                     Jc[1][3 + j] = D[1][j];
                 }
+            }
+            if constexpr (NP == 11) {  // d/d(fx, fy, skew, cx, cy) = (q0, 0, q1, q2, 0) / q2 | (0, q1, 0, 0, q2) / q2
+                const double p0 = q0 * iz, p1 = q1 * iz;
+                Jc[0][6] = p0;  Jc[0][7] = 0.0; Jc[0][8] = p1;  Jc[0][9] = 1.0; Jc[0][10] = 0.0;
+                Jc[1][6] = 0.0; Jc[1][7] = p1;  Jc[1][8] = 0.0; Jc[1][9] = 0.0; Jc[1][10] = 1.0;
             }
 #pragma unroll
             for (int j = 0; j < 3; ++j) {

@@ -346,7 +346,77 @@ __device__ __forceinline__ void schur_diag_walk(const ObsArgs& a, const double2*
 #define SATBA_PAIRS_OCC_MIN_O 1  // perspective / RPC kernels: least waves per SIMD the register allocator must leave room for (218 - 252 registers: two
                                  // waves.  Round 5, forced to 3 -- 168 registers, 88 - 340 bytes of scratch in the hit loop: C5 1 419 against 1 699 it/s, P3 1 209 / 2 324)
 #endif
-#define SATBA_PAIRS_WAVES_ATTR(MODEL, UNITW) __attribute__((amdgpu_waves_per_eu(((MODEL) == AFFINE) ? ((UNITW) ? SATBA_PAIRS_OCC_U : SATBA_PAIRS_OCC_W) : SATBA_PAIRS_OCC_MIN_O, ((MODEL) == AFFINE) ? ((UNITW) ? SATBA_PAIRS_OCC_U : SATBA_PAIRS_OCC_W) : 3)))
+// (NP > 6, the intrinsics: the NP x NP accumulators alone are 128 / 242 registers -- the affine kernel takes the generic form and the bounds of
+// the perspective ones)
+#define SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) __attribute__((amdgpu_waves_per_eu(((MODEL) == AFFINE && (NP) <= 6) ? ((UNITW) ? SATBA_PAIRS_OCC_U : SATBA_PAIRS_OCC_W) : SATBA_PAIRS_OCC_MIN_O, ((MODEL) == AFFINE && (NP) <= 6) ? ((UNITW) ? SATBA_PAIRS_OCC_U : SATBA_PAIRS_OCC_W) : 3)))
+// End of a pair item whose block has more than 64 entries (perspective cameras with intrinsics, NP = 11): the block is reduced in passes
+// of 64 totals (one per lane) and published like the single-pass epilogue of schur_pairs_body does it -- plain stores, or the chunk
+// partials and the arrival counts of the factorisation beside the kernel (one arrival per item, after every pass is out).
+template <int NP, bool UNITW>
+__device__ __forceinline__ void schur_pairs_epilogue_wide(const ObsArgs& a, const SchurArgs& s, double* __restrict__ S, const unsigned bidx, const int lane,
+                                                          const int i, const int j, const int chunk, const long long pair, const long long n_pairs,
+                                                          const double (&acc)[NP][NP]) {
+    constexpr int NB2 = NP * NP, NPS = (NB2 + 63) / 64;
+    const double cam_mask = (i < a.n_cam_fix || j < a.n_cam_fix) ? 0.0 : 1.0;
+    double total[NPS];
+    int ev[NPS];
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) {
+        double flat[64];
+#pragma unroll
+        for (int e = 0; e < 64; ++e) flat[e] = (64 * ps + e < NB2) ? acc[(64 * ps + e) / NP][(64 * ps + e) % NP] : 0.0;
+        total[ps] = cam_mask * wave_reduce_scatter<64>(flat, lane, 32);
+        ev[ps] = 64 * ps + rs_index<64>(lane);
+    }
+    if (s.arrive && bidx == 0 && threadIdx.x == 0)
+        __hip_atomic_store(s.arrive + (size_t)SCHUR_ARRIVE_STRIDE * a.M, s.arrive_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    auto out = [&](int e) { return S + (size_t)(j * NP + e % NP) + (size_t)(i * NP + e / NP) * a.n_c; };
+    const size_t stride = (size_t)n_pairs * NB2;
+    double* const part = s.pair_part + ((size_t)chunk * n_pairs + pair) * NB2;
+    if (!UNITW && s.arrive && s.n_chunks > 1) {  // chunk partials beside the factorisation (schur_pair_publish, NPS totals per lane)
+#pragma unroll
+        for (int ps = 0; ps < NPS; ++ps)
+            if (ev[ps] < NB2) __hip_atomic_store(part + ev[ps], total[ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int* cnt = s.pair_cnt + pair;
+        if (chunk + 1 < s.n_chunks) {
+            if (lane == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        if (lane == 0) {
+            int spins = 0;
+            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < s.n_chunks - 1) {
+                __builtin_amdgcn_s_sleep(4);
+                if (++spins > (1 << 22)) { atomicOr(s.fail, 2); break; }
+            }
+            __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int ps = 0; ps < NPS; ++ps) {
+            if (ev[ps] >= NB2) continue;
+            const double* first = part - (size_t)chunk * stride + ev[ps];
+            double t = 0.0;
+            for (int ch = 0; ch < s.n_chunks; ++ch) t += __hip_atomic_load(first + (size_t)ch * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(out(ev[ps]), t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(s.arrive + (size_t)SCHUR_ARRIVE_STRIDE * i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) {
+        if (ev[ps] >= NB2) continue;
+        if (s.n_chunks > 1) part[ev[ps]] = total[ps];
+        else if (!s.arrive) *out(ev[ps]) = total[ps];
+        else __hip_atomic_store(out(ev[ps]), total[ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (s.arrive && s.n_chunks == 1) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(s.arrive + (size_t)SCHUR_ARRIVE_STRIDE * i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // bidx: the workgroup's index among the pair workgroups of the launch; s_coop: 4 x 64 x 7 double2 of LDS -- per wave 64 records x 80 (112: with the
 // scales) bytes, or 64 Jacobian rows x 112 (the cooperative gathers are transposed here); s_idx: weighted / robust, the three gather indices of a wave's 64 hits
 template <int MODEL, int NP, bool UNITW>
@@ -367,8 +437,24 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
             for (int k = 0; k < CU; ++k) dacc[k] = 0.0;
             schur_diag_walk<MODEL, NP, 64>(a, s.PV, s.cm_rec, s.cm_sc, 1, s.zero_fix, i, (int)dp->lo, (int)dp->hi, lane,
                                            reinterpret_cast<double2*>(reinterpret_cast<char*>(s_coop) + wave * (64 * 112)), dacc);
-            double flat[CPAD];
             const double cam_mask = i < a.n_cam_fix ? 0.0 : 1.0;
+            if constexpr (CU > 32) {  // intrinsics (NP = 8, 11: 44, 77 sums): passes of 64 totals, one per lane
+#pragma unroll
+                for (int o = 0; o < CU; o += 64) {
+                    double flat[64];
+#pragma unroll
+                    for (int e = 0; e < 64; ++e) flat[e] = (o + e < CU) ? dacc[o + e] : 0.0;
+                    const double total = cam_mask * wave_reduce_scatter<64>(flat, lane, 32);
+                    const int e = o + rs_index<64>(lane);
+                    double* const mine = s.dg_part + ((size_t)i * s.n_dg + chunk) * CU + e;
+                    if (e < CU) {
+                        if (!s.arrive) *mine = total;
+                        else __hip_atomic_store(mine, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                if (!s.arrive) return;
+            } else {
+            double flat[CPAD];
 #pragma unroll
             for (int e = 0; e < CPAD; ++e) flat[e] = (e < CU) ? dacc[e] : 0.0;
             const double total = cam_mask * wave_reduce_scatter<CPAD>(flat, lane, 32);
@@ -380,6 +466,7 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
                 return;
             }
             if (writer) __hip_atomic_store(mine, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (bidx == 0 && threadIdx.x == 0)  // (the first item of the launch: everything in front of this kernel on the stream is complete)
                 __hip_atomic_store(s.arrive + (size_t)SCHUR_ARRIVE_STRIDE * a.M, s.arrive_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -426,9 +513,11 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
     // -- 120 multiply-adds per hit instead of 198 for the generic form below (two full Jacobian evaluations, 2 x 5 blocks).
     // P_i, P_j: unit weights: A^T A R (so that m' = P_i Vinv P_j^T directly); otherwise A R, and A_i^T . A_j is applied after
     // the row scales.  Wave-uniform, computed once per item.
+    // NP = 8 (intrinsics): their columns (q0, q1) are not of the form [D | I]; the generic form below
+    constexpr bool AFAC = MODEL == AFFINE && NP <= 5;
     double Pi_[2][3], Pj_[2][3], Ai_[3] = {0.0, 0.0, 0.0}, Aj_[3] = {0.0, 0.0, 0.0};
     double tri[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, trj[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // cos, sin of the three angles
-    if constexpr (MODEL == AFFINE) {
+    if constexpr (AFAC) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) { tri[k] = cci[k]; trj[k] = ccj[k]; }
         // (wave-uniform values computed by the vector ALU go back to scalar registers: 12 doubles that live through the whole loop)
@@ -465,7 +554,7 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
     auto compute = [&](const Rec& rc, int pi, int pj, const double2& scl_i, const double2& scl_j, const double* tip, const double* tjp) {
         const double X = rc.r0.x, Y = rc.r0.y, Z = rc.r1.x;
         const double v00 = rc.r1.y, v01 = rc.r2.x, v02 = rc.r2.y, v11 = rc.r3.x, v12 = rc.r3.y, v22 = rc.r4;
-        if constexpr (MODEL == AFFINE) {
+        if constexpr (AFAC) {
             double T[2][3];  // P_i Vinv
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
@@ -702,7 +791,12 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
 
     // wave reduction of the NP x NP block; block (row j, col i) of the column-major lower triangle
     constexpr int NB2 = NP * NP;
+    if constexpr (NB2 > 64) {  // perspective with intrinsics (121 entries)
+        schur_pairs_epilogue_wide<NP, UNITW>(a, s, S, bidx, lane, i, j, chunk, pair, n_pairs, acc);
+        return;
+    }
     constexpr int NPAD = NB2 <= 16 ? 16 : (NB2 <= 32 ? 32 : 64);
+    static_assert(NB2 <= NPAD || NB2 > 64, "pair block reduction");
     double flat[NPAD];
 #pragma unroll
     for (int e = 0; e < NPAD; ++e) flat[e] = (e < NB2) ? acc[e / NP][e % NP] : 0.0;
@@ -738,7 +832,7 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
     }
 }
 template <int MODEL, int NP, bool UNITW>
-__global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, UNITW) void k_schur_pairs(ObsArgs a, SchurArgs s, double* __restrict__ S) {
+__global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) void k_schur_pairs(ObsArgs a, SchurArgs s, double* __restrict__ S) {
     SATBA_GATE(a.gate);
     __shared__ double2 s_coop[4 * 64 * 7];
     __shared__ unsigned s_idx[4][3 * 64];
@@ -799,8 +893,9 @@ __device__ __forceinline__ void schur_diag_walk(const ObsArgs& a, const double2*
         return r;
     };
     // affine cameras (block-uniform): J_c = A [D(X) | I], J_p = A R  (see k_schur_pairs)
+    constexpr bool AFAC = MODEL == AFFINE && NP <= 5;  // (NP = 8: the intrinsics' columns are not of the form [D | I]: generic form)
     double Pm[2][3], Au[3] = {0.0, 0.0, 0.0}, tr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if constexpr (MODEL == AFFINE) {
+    if constexpr (AFAC) {
         const double fx = cc[CAMX + 2], fy = cc[CAMX + 3], sk = cc[CAMX + 4];
         Au[0] = fx; Au[1] = sk; Au[2] = fy;
 #pragma unroll
@@ -839,7 +934,7 @@ __device__ __forceinline__ void schur_diag_walk(const ObsArgs& a, const double2*
             double sx = vm, sy = vm;  // squared row scales times the fixed-point mask, applied to the 2 x 2 middle matrix
             double ux = vm, uy = vm;  // squared row scales on the J_c^T J_c term (no point mask there)
             const double v00 = r1.y, v01 = r2.x, v02 = r2.y, v11 = r3.x, v12 = r3.y, v22 = r4.x;
-            if constexpr (MODEL == AFFINE) {
+            if constexpr (AFAC) {
                 if (a.sc) { const double2 t = sc_now; ux = vm * t.x * t.x; uy = vm * t.y * t.y; }
                 sx = ux; sy = uy;  // the fixed-point mask rides in the record's Vinv
                 double T[2][3];  // J_p Vinv
@@ -990,7 +1085,7 @@ __global__ __launch_bounds__(LINC_THREADS) void k_schur_diag(ObsArgs a, CamMajor
 // (n_diag_pad: n_diag rounded up to a multiple of 8, so that a pair workgroup's index keeps its XCD), the rest the pair kernel's.
 static_assert(LINC_THREADS == 256, "k_schur_both: both bodies run 256 threads");
 template <int MODEL, int NP, bool UNITW>
-__global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, UNITW) void k_schur_both(ObsArgs a, CamMajor c, SchurArgs s, double* __restrict__ part, double* __restrict__ S,
+__global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) void k_schur_both(ObsArgs a, CamMajor c, SchurArgs s, double* __restrict__ part, double* __restrict__ S,
                                                                                       int n_diag, int n_diag_pad, int M, int n_chunks) {
     SATBA_GATE(a.gate);
     __shared__ double2 s_coop[4 * 64 * 7];

@@ -96,7 +96,7 @@ def _surviving_tracks(pts_ind, cam_ind, n_pts, n_cam, pairs_to_triangulate):
 
 def _options_like(p, n_pts_fix, verbose):
     return {"n_cam_fix": int(p.n_cam_fix), "n_pts_fix": int(n_pts_fix), "reduce": False, "verbose": verbose,
-            "correction_params": p.cam_params_to_optimize, "ref_cam_weight": p.ref_cam_weight}
+            "correction_params": p.cam_params_to_optimize, "ref_cam_weight": p.ref_cam_weight, "K_init": getattr(p, "K_init", None)}
 
 
 def reset_ba_params_after_outlier_removal(C_new, p, verbose=True, pts3d=None):

@@ -11,7 +11,8 @@ altogether at the 10 M-observation scale.
 
 Variable vector layout (ref:bundle_adjust/ba_params.py:152-172):
     params_opt = [ cam 0 (n_params) | ... | cam M-1 (n_params) | pt 0 (3) | ... | pt N-1 (3) ]
-with n_params = 3 for ["R"], 5 (affine) or 6 (perspective, rpc) for ["R", "T"].
+with n_params = 3 for ["R"], 5 (affine) or 6 (perspective, rpc) for ["R", "T"], and 8 (affine) or 11 (perspective) for
+["R", "T", "K"] with the option K_init="camera": the first n_params columns of `cam_params` (angles, T, then the intrinsics).
 Per-camera parameter rows `cam_params` (ref:bundle_adjust/ba_params.py:19-44):
     affine       [a, b, g, t0, t1, fx, fy, skew]                     (8)
     perspective  [a, b, g, t0, t1, t2, fx, fy, skew, cx, cy]         (11)
@@ -27,6 +28,8 @@ class Error(Exception):
 
 
 _N_T = {"affine": 2, "perspective": 3, "rpc": 3}
+_N_K = {"affine": 3, "perspective": 5}  # fx, fy, skew (, cx, cy): the columns behind T in `cam_params`
+_K_INIT = ("camera",)
 
 
 def load_cam_params_from_camera(camera, camera_center, cam_model):
@@ -84,7 +87,8 @@ class BundleAdjustmentParameters:
             pairs_to_triangulate: list of camera index pairs
             camera_centers: list of M 3-vectors
             d: options -- "n_cam_fix", "n_pts_fix", "reduce" (True), "verbose" (True),
-               "correction_params" (["R"]), "ref_cam_weight" (1.0)
+               "correction_params" (["R"]), "ref_cam_weight" (1.0), "K_init" (None; "camera": refine
+               the intrinsics, see _init_options)
         """
         self._init_options(cam_model, d)
         self.C = C.copy()
@@ -151,10 +155,20 @@ class BundleAdjustmentParameters:
         self.ref_cam_weight = d.get("ref_cam_weight", 1.0)
         self.n_cam_fix = d.get("n_cam_fix", 0)
         self.n_pts_fix = d.get("n_pts_fix", 0)
-        if "K" in self.cam_params_to_optimize:
-            # ref:bundle_adjust/ba_params.py:163 slices the T columns a second time instead of K
-            # (SURVEY.md section 0, fact 3): there is no well-defined behaviour to reproduce.
-            raise Error('correction_params containing "K" / "COMMON_K" are not supported')
+        self.K_init = d.get("K_init", None)
+        if self.K_init is not None and self.K_init not in _K_INIT:
+            raise Error("unknown K_init {!r} (known: {})".format(self.K_init, ", ".join(map(repr, _K_INIT))))
+        if "K" in self.cam_params_to_optimize or "COMMON_K" in self.cam_params_to_optimize:
+            # ref:bundle_adjust/ba_params.py:163 starts K from the T columns a second time: there is
+            # no well-defined behaviour to reproduce.  K_init="camera" opts in to the corrected start (K from each camera's own
+            # calibration); everything else of the reference's K machinery (get_vars_ready_for_fun, fun) is followed as it is.
+            if self.K_init is None:
+                raise Error('correction_params containing "K" / "COMMON_K" need the option K_init="camera" '
+                            "(the reference starts K from the T columns)")
+            if "COMMON_K" in self.cam_params_to_optimize:
+                raise Error('"COMMON_K" (one K shared by all cameras) is not supported')
+            if cam_model not in _N_K:
+                raise Error('"K" is not defined for cam_model {!r}'.format(cam_model))
 
     def _finish(self, verbose):
         self.cam_params = np.array(
@@ -168,6 +182,8 @@ class BundleAdjustmentParameters:
             self.n_params = 3
             if "T" in self.cam_params_to_optimize:
                 self.n_params += _N_T[self.cam_model]
+                if "K" in self.cam_params_to_optimize:  # (checked in _init_options: K_init given, affine / perspective)
+                    self.n_params += _N_K[self.cam_model]
         else:
             # the reference builds `cam_params_opt = []` here and fails on `cam_params_opt.ravel()` (AttributeError,
             # ref:bundle_adjust/ba_params.py:152-170): there is no behaviour to reproduce, only a clearer message

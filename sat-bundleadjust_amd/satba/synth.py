@@ -8,6 +8,7 @@ reference's (2M, N) correspondence matrix for the small cases that go through th
 Named shapes (affine):  C2 = (10, 5000, 6, seed 1) -> 29 878 observations
                         C3 = (50, 100 000, 10, seed 1) -> ~1 M
                         C4 = (200, 1 000 000, 10, seed 1) -> ~10 M
+With the intrinsics refined as well (R + T + K): C3K (affine) and P3K (perspective), the C3 / P3 scenes.
 """
 import os
 
@@ -18,13 +19,28 @@ from .rpc_model import RPCModel
 
 SCENE_CENTRE = np.array([1.7e6, -5.9e6, 1.2e6])  # ECEF-scale magnitudes, metres
 
+class CorrectionWithK(list):
+    """
+    correction_params of the named K configs: make_params opts them in with K_init="camera" (a plain list is passed on as it is, so a
+    plain ["R", "T", "K"] still raises ba_params.Error without the option).  The mark is the type: a copy (list(c), c[:], c + [...])
+    is a plain list and loses it -- callers that build their options from CONFIGS pass the entry itself, as bench.py does.
+    """
+
+
 SHAPES = {"C2": (10, 5000, 6), "C3": (50, 100000, 10), "C4": (200, 1000000, 10)}
 # BASELINE.json configs by name: (camera model, correction_params, n_cam, n_pts, obs_per_pt)
 CONFIGS = {"C2": ("affine", ["R", "T"], 10, 5000, 6), "C3": ("affine", ["R", "T"], 50, 100000, 10),
            "C4": ("affine", ["R", "T"], 200, 1000000, 10), "C5": ("rpc", ["R"], 50, 100000, 10),
            "P3": ("perspective", ["R", "T"], 50, 100000, 10),
            # between C3 and C4 (tuning of thresholds that depend on the number of cameras; not bench lines)
-           "M100": ("affine", ["R", "T"], 100, 300000, 10), "M150": ("affine", ["R", "T"], 150, 600000, 10)}
+           "M100": ("affine", ["R", "T"], 100, 300000, 10), "M150": ("affine", ["R", "T"], 150, 600000, 10),
+           # refinement of the intrinsics as well (R + T + K: 8 / 11 parameters per camera; make_params adds K_init="camera" for a
+           # CorrectionWithK -- the entry itself, not a copy of it)
+           "C3K": ("affine", CorrectionWithK(["R", "T", "K"]), 50, 100000, 10),
+           "P3K": ("perspective", CorrectionWithK(["R", "T", "K"]), 50, 100000, 10)}
+# stream of the intrinsics' errors (sigma_k): a generator of its own, so that the scenes without it -- and every golden built from one --
+# keep their bits
+_K_STREAM = 0x4B
 
 
 class Scene:
@@ -86,9 +102,18 @@ def rotate_points(X, angles):
     return np.stack((x, y, z), axis=1)
 
 
+def _k_errors(seed, n_cam, sigma_k):
+    """(n_cam, 5) standard normal draws of the intrinsics' errors, or None (sigma_k = 0: the initial cameras carry the true K)."""
+    if not sigma_k:
+        return None
+    return np.random.default_rng([seed, _K_STREAM]).normal(0.0, 1.0, (n_cam, 5))
+
+
 def make_affine_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, noise_px=0.3, pts_noise_m=2.0,
-                      pts_float32=False):
+                      pts_float32=False, sigma_k=0.0):
+    """sigma_k: relative error of the initial cameras' fx, fy (and absolute error of the skew), K_true in `cams_K_true`."""
     rng = np.random.default_rng(seed)
+    ek = _k_errors(seed, n_cam, sigma_k)
     c = SCENE_CENTRE
     pts_true = c + rng.uniform(-5e3, 5e3, (n_pts, 3))
     angles = rng.uniform(-0.5, 0.5, (n_cam, 3))
@@ -101,7 +126,10 @@ def make_affine_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, noise_
         R = ba_rotate.euler_angles_to_R(*angles[i])
         T = -R[:2] @ c + shift[i]
         cams_true.append(cam_utils.compose_affine_camera(K, R, T))
-        cams_init.append(cam_utils.compose_affine_camera(K, ba_rotate.euler_angles_to_R(*(angles[i] + dtheta[i])), T))
+        Ki = K
+        if ek is not None:
+            Ki = np.array([[K[0, 0] * (1 + sigma_k * ek[i, 0]), K[0, 1] + sigma_k * ek[i, 2]], [0.0, K[1, 1] * (1 + sigma_k * ek[i, 1])]])
+        cams_init.append(cam_utils.compose_affine_camera(Ki, ba_rotate.euler_angles_to_R(*(angles[i] + dtheta[i])), T))
     pts_ind, cam_ind = _visibility(rng, n_cam, n_pts, obs_per_pt)
     proj = _project_linear(np.stack(cams_true), 2, cam_ind, pts_true[pts_ind])
     pts2d = proj + rng.normal(0.0, noise_px, proj.shape)
@@ -113,9 +141,13 @@ def make_affine_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, noise_
                  camera_centers=[np.zeros(3) for _ in range(n_cam)], pairs_to_triangulate=[(0, 1)])
 
 
-def make_perspective_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, noise_px=0.3, pts_noise_m=2.0):
-    """Pinhole cameras ~600 km above the scene looking at its centre, ~1 px per metre."""
+def make_perspective_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, noise_px=0.3, pts_noise_m=2.0, sigma_k=0.0):
+    """
+    Pinhole cameras ~600 km above the scene looking at its centre, ~1 px per metre.  sigma_k: relative error of the initial
+    cameras' fx, fy, cx, cy (the skew: absolute, sigma_k x 10 px).
+    """
     rng = np.random.default_rng(seed)
+    ek = _k_errors(seed, n_cam, sigma_k)
     c = SCENE_CENTRE
     up = c / np.linalg.norm(c)
     pts_true = c + rng.uniform(-5e3, 5e3, (n_pts, 3))
@@ -133,8 +165,12 @@ def make_perspective_scene(n_cam, n_pts, obs_per_pt, seed=1, sigma_theta=2e-6, n
         a = np.array(ba_rotate.euler_angles_from_R(R))
         vecT = -(R @ oC)
         Rn = ba_rotate.euler_angles_to_R(*(a + rng.normal(0, sigma_theta, 3)))
-        for Ri, out in ((R, cams_true), (Rn, cams_init)):
-            P = K @ np.hstack((Ri, vecT.reshape(3, 1)))
+        Kn = K
+        if ek is not None:
+            Kn = np.array([[K[0, 0] * (1 + sigma_k * ek[i, 0]), K[0, 1] + 10.0 * sigma_k * ek[i, 2], K[0, 2] * (1 + sigma_k * ek[i, 3])],
+                           [0.0, K[1, 1] * (1 + sigma_k * ek[i, 1]), K[1, 2] * (1 + sigma_k * ek[i, 4])], [0, 0, 1.0]])
+        for Ri, Ki, out in ((R, K, cams_true), (Rn, Kn, cams_init)):
+            P = Ki @ np.hstack((Ri, vecT.reshape(3, 1)))
             out.append(P / P[2, 3])
         centers.append(oC)
     pts_ind, cam_ind = _visibility(rng, n_cam, n_pts, obs_per_pt)
@@ -202,6 +238,8 @@ def make_params(scene, d=None, dense=False):
     from .ba_params import BundleAdjustmentParameters
 
     d = dict({"verbose": False}, **(d or {}))
+    if isinstance(d.get("correction_params"), CorrectionWithK):  # (CONFIGS C3K / P3K: the intrinsics start from the cameras)
+        d.setdefault("K_init", "camera")
     if dense:
         return BundleAdjustmentParameters(scene.to_dense_C(), scene.pts3d, scene.cameras, scene.cam_model,
                                           scene.pairs_to_triangulate, scene.camera_centers, d)
