@@ -305,6 +305,34 @@ int satba_init_pts3d(int32_t cam_model, int32_t n_cam, int64_t n_pts, const int6
 int satba_init_pts3d_resident(satba_problem *p, const uint8_t *remove, const double *cameras, int32_t n_pairs,
                               const int32_t *pairs, float *pts3d, int32_t *n_tri, float *kernel_ms);
 
+/* ---- selection of the feature tracks, the step between the triangulation and the path (ft_ranking.py).  Stand-alone: no
+ * problem handle.  The tracks come as the lists of the triangulation entry above: pt_ofs (host, n_pts + 1, pt_ofs[0] = 0), cam_ind
+ * (host, K; cameras ascend strictly inside a track), plus scale and err (host, K: keypoint scale and reprojection error of every
+ * observation; err == NULL: zeros, as ba_pipeline.py does while there are no 3-D points).
+ *
+ * satba_track_keys: the three ranking keys of ft_ranking.order_tracks (ft_ranking.py:145-147): length (observations), key_scale
+ * (np.round of the mean scale to 2 decimals), key_cost (mean error); bit-identical to numpy's given the same inputs.
+ *
+ * satba_track_connectivity replaces ft_ranking.build_connectivity_matrix (ft_ranking.py:19-34): A (host, n_cam x n_cam int32) =
+ * tracks seen by both cameras, zero diagonal, entries below min_matches zeroed (:32).  alive (host, n_pts bytes, may be NULL):
+ * tracks with a zero byte are left out.
+ *
+ * satba_select_tracks replaces ft_ranking.select_best_tracks (ft_ranking.py:136-153 order_tracks, :232-263 get_tracks, :197-229
+ * get_tracks_current_tree, :83-118 compute_camera_weights): K spanning trees over the camera graph, each taking the best-ranked
+ * live tracks that reach new cameras.  priority: three codes, 0 length, 1 scale, 2 cost, -1 unused (the missing keys follow in
+ * that order, numpy's rule for `order=`); exact ties in all three keys put the higher track index first.  Outputs: tree_of (host,
+ * n_pts: the tree that took the track, or -1), n_selected, n_trees (trees that took at least one track; the loop ends after K
+ * trees, when no track is left, or at the first empty tree), weights (host, K x n_cam, may be NULL: the camera weights every tree
+ * started from, zero rows for trees that did not run), rank (host, n_pts, may be NULL: position of every track in the ranking),
+ * kernel_ms (may be NULL: ranking + trees on the stream from HIP events, the per-layer status reads included). */
+int satba_track_keys(int64_t n_pts, const int64_t *pt_ofs, const double *scale, const double *err, int32_t *length,
+                     double *key_scale, double *key_cost, int32_t device);
+int satba_track_connectivity(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, const int32_t *cam_ind, const uint8_t *alive,
+                             int32_t min_matches, int32_t *A, int32_t device);
+int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, const int32_t *cam_ind, const double *scale,
+                        const double *err, int32_t K, const int32_t *priority, int32_t *tree_of, int64_t *n_selected,
+                        int32_t *n_trees, double *weights, int64_t *rank, int32_t device, float *kernel_ms);
+
 /* ---- RPC re-fit after the solve, the step behind the path.  Stand-alone: no problem handle.
  * satba_rpc_fit replaces ba_rpcfit.weighted_lsq (ba_rpcfit.py:88-153, with initialize_rpc / scaling_params :156-198), batched over
  * cameras: target (host, n_cam x n_samples x 2: col, row), locs (host, n_cam x n_samples x 3: lon, lat, alt) -> tables (host,

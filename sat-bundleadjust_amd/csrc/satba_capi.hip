@@ -27,6 +27,7 @@
 #include "satba_lmdev.h"
 #include "satba_outliers.h"
 #include "satba_triangulate.h"
+#include "satba_tracks.h"
 #include "satba_rpcfit.h"
 #include "satba_schur.h"
 
@@ -985,7 +986,7 @@ static int build_layout(satba_problem* p, const satba_problem_desc* d) {
 extern "C" {
 
 const char* satba_last_error(void) { return g_err.c_str(); }
-int satba_version(void) { return 4; }
+int satba_version(void) { return 5; }
 
 int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
     Range range_("satba:problem_create");
@@ -2640,5 +2641,6 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_outliers_api.inc"
 #include "satba_triangulate_api.inc"
 #include "satba_rpcfit_api.inc"
+#include "satba_tracks_api.inc"
 
 }  // extern "C"

@@ -33,6 +33,7 @@ SYMBOLS = [
     "satba_solve_lm", "satba_lm_step", "satba_lm_run", "satba_lm_state", "satba_lm_begin", "satba_lm_part", "satba_lm_poll", "satba_profile_linearize", "satba_profile_read", "satba_outliers", "satba_layout_len", "satba_get_layout", "satba_get_info",
     "satba_triangulate_pairwise", "satba_init_pts3d", "satba_init_pts3d_resident", "satba_snapshot_x",
     "satba_rpc_fit", "satba_rpc_localization", "satba_rpc_refit",
+    "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
 ]
 
 FLAG_DETERMINISTIC = 1
@@ -149,6 +150,10 @@ def load_library(path=None):
     lib.satba_init_pts3d.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, C.c_int32, _ip, _fp, _ip,
                                      C.c_int32, C.c_int32, _fp]
     lib.satba_init_pts3d_resident.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), _dp, C.c_int32, _ip, _fp, _ip, _fp]
+    _lp = C.POINTER(C.c_int64)
+    lib.satba_track_keys.argtypes = [C.c_int64, _lp, _dp, _dp, _ip, _dp, _dp, C.c_int32]
+    lib.satba_track_connectivity.argtypes = [C.c_int32, C.c_int64, _lp, _ip, C.POINTER(C.c_uint8), C.c_int32, _ip, C.c_int32]
+    lib.satba_select_tracks.argtypes = [C.c_int32, C.c_int64, _lp, _ip, _dp, _dp, C.c_int32, _ip, _ip, _lp, _ip, _dp, _lp, C.c_int32, _fp]
     if path == LIB_PATH:
         _LIB = lib
     return lib
