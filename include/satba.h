@@ -333,6 +333,37 @@ int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, con
                         const double *err, int32_t K, const int32_t *priority, int32_t *tree_of, int64_t *n_selected,
                         int32_t *n_trees, double *weights, int64_t *rank, int32_t device, float *kernel_ms);
 
+/* ---- feature tracks from pairwise matches, the step in front of the triangulation (ft_utils.py:65-182
+ * feature_tracks_from_pairwise_matches with its baseline check :38-62 filter_C_using_pairs_to_triangulate, and the fixed-first
+ * partition of ft_pipeline.py:175-179).  Stand-alone: no problem handle; no dense matrix is built.  Keypoint k of image m has
+ * the global id kp_ofs[m] + k (kp_ofs: host, n_cam + 1, ascending from 0).  A track is a connected component (at least 2
+ * keypoints) of the graph whose edges are the match rows; where several of its keypoints lie in one image the one written last by
+ * the reference's fill wins (first-side keypoints of all rows in row order, then the second-side ones); a track stays if some
+ * camera pair (i, j), i < j, of its observations is listed in pairs (a pair listed with i >= j or naming a camera >= n_cam
+ * never matches).  Tracks are ordered by the smallest global id of their component; with n_adj > 0 the tracks without an
+ * observation in a camera >= n_adj come first (n_pts_fix of them), both groups in that order.  The order of the match rows
+ * changes nothing but the winners of contested cells, and two runs give identical bits.  A row with im_i > im_j is accepted
+ * and is the same graph edge; im_i == im_j is an argument error, like an image >= n_cam, a keypoint index outside its image, or
+ * 2^31 or more keypoints or matches.  The reference loses a union when a row names keypoint 0 of image 0 on its second side;
+ * that is not reproduced (with im_i < im_j, what ft_match produces, it cannot occur).
+ * kp: host, n_kp_total x 3 float32 (x, y, scale = columns 0..2 of the reference's keypoint arrays; NaN rows of padding are
+ * fine, they are never matched).  matches: host, n_matches x 4 int32 (kp_i, kp_j, im_i, im_j).  pairs: host, n_pairs x 2.
+ * counts (host, 5 x int64): n_tracks, n_obs, n_pts_fix, n_components (size >= 2, before the baseline check), n_conflicts
+ * ((camera, track) cells with more than one claimant, before the baseline check).  kernel_ms (may be NULL): from the first kernel to
+ * the last on the stream, from HIP events (the uploads are outside, two reads of counters inside). */
+typedef struct satba_ftracks satba_ftracks;
+int satba_ftracks_build(int32_t n_cam, const int64_t *kp_ofs, const float *kp, int64_t n_matches, const int32_t *matches,
+                        int32_t n_pairs, const int32_t *pairs, int32_t n_adj, satba_ftracks **out, int64_t *counts,
+                        int32_t device, float *kernel_ms);
+/* the lists satba_init_pts3d and satba_select_tracks take; any output may be NULL: pt_ofs (n_tracks + 1), cam_ind (n_obs int32,
+ * ascending strictly inside a track), kp_id (n_obs int32: index of the keypoint inside its image, the reference's C_v2), obs
+ * (n_obs x 2 float64: the float32 coordinates widened exactly), scale (n_obs float64) */
+int satba_ftracks_fetch(satba_ftracks *t, int64_t *pt_ofs, int32_t *cam_ind, int32_t *kp_id, double *obs, double *scale);
+void satba_ftracks_destroy(satba_ftracks *t);
+/* the baseline check alone, on lists (ft_utils.py:38-62): keep (host, n_pts bytes) = 1 where the track holds a listed pair */
+int satba_tracks_have_pair(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, const int32_t *cam_ind, int32_t n_pairs,
+                           const int32_t *pairs, uint8_t *keep, int32_t device);
+
 /* ---- RPC re-fit after the solve, the step behind the path.  Stand-alone: no problem handle.
  * satba_rpc_fit replaces ba_rpcfit.weighted_lsq (ba_rpcfit.py:88-153, with initialize_rpc / scaling_params :156-198), batched over
  * cameras: target (host, n_cam x n_samples x 2: col, row), locs (host, n_cam x n_samples x 3: lon, lat, alt) -> tables (host,

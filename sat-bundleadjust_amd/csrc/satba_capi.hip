@@ -28,6 +28,7 @@
 #include "satba_outliers.h"
 #include "satba_triangulate.h"
 #include "satba_tracks.h"
+#include "satba_ftracks.h"
 #include "satba_rpcfit.h"
 #include "satba_schur.h"
 
@@ -2642,5 +2643,6 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_triangulate_api.inc"
 #include "satba_rpcfit_api.inc"
 #include "satba_tracks_api.inc"
+#include "satba_ftracks_api.inc"
 
 }  // extern "C"

@@ -34,6 +34,7 @@ SYMBOLS = [
     "satba_triangulate_pairwise", "satba_init_pts3d", "satba_init_pts3d_resident", "satba_snapshot_x",
     "satba_rpc_fit", "satba_rpc_localization", "satba_rpc_refit",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
+    "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
 ]
 
 FLAG_DETERMINISTIC = 1
@@ -154,6 +155,11 @@ def load_library(path=None):
     lib.satba_track_keys.argtypes = [C.c_int64, _lp, _dp, _dp, _ip, _dp, _dp, C.c_int32]
     lib.satba_track_connectivity.argtypes = [C.c_int32, C.c_int64, _lp, _ip, C.POINTER(C.c_uint8), C.c_int32, _ip, C.c_int32]
     lib.satba_select_tracks.argtypes = [C.c_int32, C.c_int64, _lp, _ip, _dp, _dp, C.c_int32, _ip, _ip, _lp, _ip, _dp, _lp, C.c_int32, _fp]
+    lib.satba_ftracks_build.argtypes = [C.c_int32, _lp, _fp, C.c_int64, _ip, C.c_int32, _ip, C.c_int32, C.POINTER(C.c_void_p), _lp, C.c_int32, _fp]
+    lib.satba_ftracks_fetch.argtypes = [C.c_void_p, _lp, _ip, _ip, _dp, _dp]
+    lib.satba_ftracks_destroy.argtypes = [C.c_void_p]
+    lib.satba_ftracks_destroy.restype = None
+    lib.satba_tracks_have_pair.argtypes = [C.c_int32, C.c_int64, _lp, _ip, C.c_int32, _ip, C.POINTER(C.c_uint8), C.c_int32]
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -11,7 +11,7 @@ libsatba_hip.so or without a GPU the calls raise.
 `select_best_tracks_from_observations` is the same selection for callers that hold observation lists (BundleAdjustmentParameters:
 pts_ind / cam_ind) with one keypoint scale and one reprojection error per observation, and never build the dense matrices.
 
-Not here: `compute_C_scale` (reads keypoint files: host I/O) and `print_quick_camera_weights`.
+Not here: `compute_C_scale` (reads keypoint files: host I/O; see satba.ft_utils) and `print_quick_camera_weights`.
 """
 import ctypes as ct
 import timeit
