@@ -369,6 +369,8 @@ int satba_tracks_have_pair(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, 
  * cameras: target (host, n_cam x n_samples x 2: col, row), locs (host, n_cam x n_samples x 3: lon, lat, alt) -> tables (host,
  * n_cam x SATBA_RPC_TABLE_LEN records of the fitted models), rmse (host, n_cam, may be NULL: the loop's last RMSE in pixels),
  * iters (host, n_cam, may be NULL: re-weighted passes that ran).  h, tol, max_iter: the reference's defaults are 1e-3, 1e-2, 20.
+ * The loop stops when the RMSE of two consecutive RE-WEIGHTED passes differs by less than tol (at least two run when max_iter
+ * allows): the unweighted solve's RMSE is no measure of the re-weighting's convergence.
  * satba_rpc_localization replaces rpcm.RPCModel.localization as ba_rpcfit.py:245,323 calls it: image points at given altitudes
  * -> lon, lat by inverting the projection of one camera (table: one record). */
 int satba_rpc_fit(int32_t n_cam, int32_t n_samples, const double *target, const double *locs, double h, double tol,

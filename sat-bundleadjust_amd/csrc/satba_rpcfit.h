@@ -191,7 +191,12 @@ __global__ __launch_bounds__(FIT_THREADS) void k_rpc_fit(int n, const double* __
         const double prev = rmse;
         rmse = sqrt(0.5 * (se_c / n + se_r / n));
         iters = pass;
-        if (pass > 0 && fabs(prev - rmse) < tol) break;
+        // Convergence is judged between two RE-WEIGHTED passes.  The reference also compares the first one with the unweighted solve
+        // (ba_rpcfit.py:146-151), but its numpy.linalg.inv leaves that solve's RMSE far above tol, so it never stops there: it runs
+        // 2 - 3 passes on every input seen.  This solve is accurate (RMSE ~1e-4 px at once), the comparison would end the fit after ONE
+        // pass, whose weights are the denominators of the unregularised solve -- rounding noise in the near-null space of the normal
+        // matrix: a model with up to 4 x the reference's fit error that answers to the last bits of the target.
+        if (pass > 1 && fabs(prev - rmse) < tol) break;
     }
     if (tid < 80) {  // record: col_num col_den row_num row_den | lon lat alt col row (offset, scale)
         tables[(size_t)cam * 90 + tid] = s_coef[tid / 40][tid % 40];
