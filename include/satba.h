@@ -255,7 +255,8 @@ int satba_lm_poll(satba_problem* p, int64_t* out, int32_t n);
 /* ---- outlier rejection between the two solves of the pipeline (ba_outliers.py:14-58, 112-155): per-camera elbow threshold
  * on the reprojection errors of the current x and the observations above it.
  * err (host, K, caller's observation order, may be NULL: computed from the residuals at the current x as
- * ba_core.compute_reprojection_error does); predef_thr < 0: automatic (elbow) thresholds; outputs: cam_thr (host, M),
+ * ba_core.compute_reprojection_error does); predef_thr < 0: automatic (elbow) thresholds, NaN: SATBA_E_ARG (a caller that means a
+ * negative threshold gets no silent elbow rule: the Python layer refuses both); outputs: cam_thr (host, M),
  * remove (host, K bytes: 1 = observation is an outlier), n_removed. */
 int satba_outliers(satba_problem *p, const double *err, double predef_thr, double min_thr, double *cam_thr, uint8_t *remove,
                    int64_t *n_removed);

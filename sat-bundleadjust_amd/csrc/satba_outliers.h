@@ -4,8 +4,8 @@
 //
 // The elbow of a camera is the sorted error value farthest from the chord between the smallest and the largest one.  The
 // removed set must come out index-exact against the reference, so the distance is evaluated with the reference's own
-// sequence of IEEE operations (numpy evaluates every step separately: no fused multiply-adds here) and ties go to the
-// first index like np.argmax.
+// sequence of IEEE operations (numpy evaluates every step separately: no fused multiply-adds here -- k_out_elbow and k_out_err_ell
+// switch contraction off and write the operators out) and ties go to the first index like np.argmax.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -38,9 +38,15 @@ __global__ void k_out_scatter_ell(long long K, const int* __restrict__ obs_pos, 
 //   thr = success ? max(elbow, min_thr) : v[n - 1];  cam_thr = round(thr, 2)
 __global__ __launch_bounds__(256) void k_out_elbow(const int* __restrict__ cam_ofs, const double* __restrict__ sorted, double predef_thr,
                                                    double min_thr, double* __restrict__ cam_thr) {
+    // no contraction: the removed set is index-exact only if every product and sum rounds where numpy's does.  HIP's __dmul_rn /
+    // __dadd_rn / __dsub_rn are inline functions around the plain operators and carry the translation unit's default
+    // (-ffp-contract=fast), so the compiler fused their products into the sums that follow -- the kernel was written with them until the
+    // plateau vectors of tests/cases_outliers.py (maxima that only rounding tells apart) and the two-point camera showed another argmax
+    // than numpy's.  The operators below are written out under the pragma, like k_out_err_ell's.
+#pragma clang fp contract(off)
     const int cam = blockIdx.x;
     if (predef_thr >= 0.0) {
-        if (threadIdx.x == 0) cam_thr[cam] = __ddiv_rn(rint(__dmul_rn(predef_thr, 100.0)), 100.0);
+        if (threadIdx.x == 0) cam_thr[cam] = __ddiv_rn(rint(predef_thr * 100.0), 100.0);
         return;
     }
     const int b = cam_ofs[cam], n = cam_ofs[cam + 1] - b;
@@ -50,16 +56,20 @@ __global__ __launch_bounds__(256) void k_out_elbow(const int* __restrict__ cam_o
         return;
     }
     // chord from (0, v0) to (n - 1, v_last), normalised (numpy: line_vec / sqrt(sum(line_vec ** 2)))
-    const double lx = (double)(n - 1), ly = __dsub_rn(v[n - 1], v[0]);
-    const double nrm = __dsqrt_rn(__dadd_rn(__dmul_rn(lx, lx), __dmul_rn(ly, ly)));
+    const double lx = (double)(n - 1), ly = v[n - 1] - v[0];
+    const double lxx = lx * lx, lyy = ly * ly;
+    const double nrm = __dsqrt_rn(lxx + lyy);
     const double ux = __ddiv_rn(lx, nrm), uy = __ddiv_rn(ly, nrm);
     double best = -1.0;
     int best_i = 0x7fffffff;
     for (int i = threadIdx.x; i < n; i += 256) {
-        const double px = (double)i, py = __dsub_rn(v[i], v[0]);
-        const double sp = __dadd_rn(__dmul_rn(px, ux), __dmul_rn(py, uy));
-        const double qx = __dsub_rn(px, __dmul_rn(sp, ux)), qy = __dsub_rn(py, __dmul_rn(sp, uy));
-        const double d = __dsqrt_rn(__dadd_rn(__dmul_rn(qx, qx), __dmul_rn(qy, qy)));
+        const double px = (double)i, py = v[i] - v[0];
+        const double pxu = px * ux, pyu = py * uy;
+        const double sp = pxu + pyu;
+        const double spx = sp * ux, spy = sp * uy;
+        const double qx = px - spx, qy = py - spy;
+        const double qxx = qx * qx, qyy = qy * qy;
+        const double d = __dsqrt_rn(qxx + qyy);
         if (d > best) { best = d; best_i = i; }  // ascending i per thread: the first maximum of the thread's subset
     }
     __shared__ double s_d[256];
@@ -82,14 +92,19 @@ __global__ __launch_bounds__(256) void k_out_elbow(const int* __restrict__ cam_o
         // (numpy/lib/_function_base_impl.py, _QuantileMethods["linear"]: get_virtual_index = (n - 1) * quantiles, NOT the generic
         // n q + (alpha + q (1 - alpha - beta)) - 1 of the other methods); checked bit for bit against np.percentile for n < 3000
         // in tests/test_host_logic.py
-        const double vi = __dmul_rn((double)(n - 1), 0.8);
+        const double vi = (double)(n - 1) * 0.8;
         const int lo = (int)floor(vi), hi = min(lo + 1, n - 1);
-        const double t = __dsub_rn(vi, (double)lo), a = v[lo], bb = v[hi], diff = __dsub_rn(bb, a);
-        double pct = __dadd_rn(a, __dmul_rn(diff, t));
-        if (t >= 0.5) pct = __dsub_rn(bb, __dmul_rn(diff, __dsub_rn(1.0, t)));
+        const double t = vi - (double)lo, a = v[lo], bb = v[hi], diff = bb - a;
+        const double dt = diff * t;
+        double pct = a + dt;
+        if (t >= 0.5) {
+            const double t1 = 1.0 - t;
+            const double d1 = diff * t1;
+            pct = bb - d1;
+        }
         const bool success = !(elbow < pct);
         const double thr = success ? fmax(elbow, min_thr) : v[n - 1];
-        cam_thr[cam] = __ddiv_rn(rint(__dmul_rn(thr, 100.0)), 100.0);  // np.round(thr, 2)
+        cam_thr[cam] = __ddiv_rn(rint(thr * 100.0), 100.0);  // np.round(thr, 2)
     }
 }
 

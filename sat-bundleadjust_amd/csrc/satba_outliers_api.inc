@@ -1,6 +1,8 @@
 // satba_outliers (include/satba.h): part of the extern "C" block of satba_capi.hip
 int satba_outliers(satba_problem* p, const double* err, double predef_thr, double min_thr, double* cam_thr, uint8_t* remove, int64_t* n_removed) {
     if (!p || !cam_thr || !remove || !n_removed) return fail(SATBA_E_ARG, "null argument");
+    // NaN is neither "< 0" (sort the errors) nor ">= 0" (skip the elbow): the elbow kernel would read a buffer nobody sorted
+    if (predef_thr != predef_thr || min_thr != min_thr) return fail(SATBA_E_ARG, "predef_thr / min_thr is NaN");
     HIP_TRY(hipSetDevice(p->device));
     const long long K = p->K;
     const Layout& L = p->L;

@@ -38,9 +38,12 @@ def compute_obs_mask(err, p, predef_thr=None, min_thr=1.0):
     """
     Per-camera thresholds and the mask of the observations to remove, on the device.
     Returns (remove (K,) bool in the order of p.pts_ind / p.cam_ind, cam_thr list of M floats, n_detected_outliers).
+    predef_thr: None or a non-negative number (ValueError otherwise).
     """
     from . import ba_core
+    from .engine_hip import check_predef_thr
 
+    check_predef_thr(predef_thr)  # (ValueError for a negative or NaN threshold, before an engine is built for it)
     eng = ba_core.get_engine(p)
     thr, remove, n = eng.outliers(np.asarray(err, dtype=np.float64), predef_thr=predef_thr, min_thr=min_thr)
     return remove, [float(t) for t in thr], n

@@ -182,6 +182,12 @@ def _check(lib, rc):
     raise SatbaError("libsatba_hip: {} (code {})".format(msg, rc))
 
 
+def check_predef_thr(predef_thr):
+    """satba_outliers takes predef_thr < 0 as "no predefined threshold": a caller's negative or NaN value must not reach it."""
+    if predef_thr is not None and not float(predef_thr) >= 0.0:
+        raise ValueError("predef_thr must be None or a non-negative number, got {!r}".format(predef_thr))
+
+
 class HipEngine:
     """Device-resident solver state of one shard (see satba/trf.py for the phase contract)."""
 
@@ -471,8 +477,10 @@ class HipEngine:
         """
         Per-camera elbow thresholds and the observations above them (ref:bundle_adjust/ba_outliers.py:112-155) for the errors
         `err` (caller's observation order; None: the reprojection errors at the current x).  Returns (cam_thr (M,),
-        remove (K,) bool, n_removed).
+        remove (K,) bool, n_removed).  predef_thr: None (elbow rule) or a non-negative number -- the C ABI spells "none" as a negative
+        value, so a negative or NaN threshold is refused here instead of silently selecting the elbow rule.
         """
+        check_predef_thr(predef_thr)
         thr = np.empty(self.n_cam)
         rm = np.zeros(max(self.n_obs, 1), dtype=np.uint8)
         n = C.c_int64()

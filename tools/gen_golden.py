@@ -588,9 +588,97 @@ def golden_reference_c():
     save("reference_c", **out)
 
 
+def save_fixed(name, **arrays):
+    """np.savez_compressed with the archive members' time stamps pinned (numpy stamps them with the wall clock): the same arrays give
+    the same bytes, so that a regenerated golden can be compared with the committed one by `cmp`."""
+    import io
+    import zipfile
+
+    path = os.path.join(OUT, name + ".npz")
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            a = np.asarray(arrays[key])
+            np.lib.format.write_array(buf, a if a.ndim == 0 else np.ascontiguousarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(arrays), "arrays")
+
+
+def golden_outliers_edges():
+    """
+    ref:bundle_adjust/ba_outliers.py:112-155 compute_obs_to_remove on every scenario of tests/cases_outliers.py: per case the thresholds
+    and the removed mask (packed bits).  The function only reads p.n_cam, p.cam_ind, p.pts_ind and p.C, so `p` is a plain namespace
+    around a layout's observation lists; the error vectors are regenerated from the builders at test time.  The reference cannot run
+    a camera without observations (IndexError in get_elbow_value): such cameras are left out of the namespace (the ones behind them
+    renumbered) and the golden holds the thresholds of the cameras that have observations, in order.
+    """
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cases_outliers as CO
+
+    out = {}
+    dense = {}
+    for key, lay, pattern, predef_thr, min_thr in CO.edge_cases():
+        L = CO.layout(lay)
+        if lay not in dense:
+            has = np.asarray(L["counts"]) > 0
+            renum = np.cumsum(has) - 1
+            cam = renum[L["cam_ind"]]
+            C = np.full((2 * int(has.sum()), L["pts3d"].shape[0]), np.nan)
+            C[2 * cam, L["pts_ind"]] = L["pts2d"][:, 0]
+            C[2 * cam + 1, L["pts_ind"]] = L["pts2d"][:, 1]
+            dense[lay] = types.SimpleNamespace(n_cam=int(has.sum()), cam_ind=cam, pts_ind=L["pts_ind"], C=C)
+        p = dense[lay]
+        err = CO.layout_errors(lay, pattern)
+        C_new, cam_thr, n = ref.ba_outliers.compute_obs_to_remove(err, p, predef_thr=predef_thr, min_thr=min_thr)
+        removed = np.isnan(C_new[2 * p.cam_ind, p.pts_ind])
+        assert int(n) == int(removed.sum())
+        out[key + "/thr"] = np.array(cam_thr, dtype=np.float64)
+        out[key + "/removed"] = np.packbits(removed)
+        print("outliers_edges", key, "removed", int(n), "thr", [float(t) for t in cam_thr][-4:], flush=True)
+    save_fixed("outliers_edges", **out)
+
+
+def import_reference_rm_outliers():
+    """What ref:bundle_adjust/ba_outliers.py:61-109 imports when it rebuilds the parameters: the reference's ft_triangulate (see
+    import_reference_triangulation) and ft_utils, whose module-level `from . import ft_match` needs OpenCV and is stubbed (nothing on
+    this path calls it)."""
+    import_reference_triangulation()
+    sys.modules.setdefault("bundle_adjust.feature_tracks.ft_match", types.ModuleType("bundle_adjust.feature_tracks.ft_match"))
+    importlib.import_module("bundle_adjust.feature_tracks.ft_utils")
+
+
+def golden_rm_outliers():
+    """ref:bundle_adjust/ba_outliers.py:158-185 rm_outliers, the reference's own, on the scenes of cases_outliers.RM_CASES: the rebuilt
+    object's observation lists, pts_prev_indices, n_pts_fix, pts3d, the thresholds, and the error vector that went in (the reference's
+    fun at the initial parameters: the removed set is index-exact only for identical errors)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cases_outliers as CO
+
+    import_reference_rm_outliers()
+    out = {}
+    for name in CO.RM_CASES:
+        scene, d, kw = CO.rm_case(name)
+        p = ref_params(scene, dict(d, reduce=False))
+        err = ref.ba_core.compute_reprojection_error(ref.ba_core.fun(p.params_opt.copy(), p), p.pts2d_w)
+        _, cam_thr, n = ref.ba_outliers.compute_obs_to_remove(err, p, **kw)
+        new_p = ref.ba_outliers.rm_outliers(err, p, verbose=False, **kw)
+        out.update({name + "/err": err, name + "/cam_thr": np.array(cam_thr, dtype=np.float64), name + "/n_detected": np.int64(n),
+                    name + "/same_object": np.bool_(new_p is p), name + "/pts_ind": new_p.pts_ind.astype(np.int32),
+                    name + "/cam_ind": new_p.cam_ind.astype(np.int32), name + "/pts2d": new_p.pts2d,
+                    name + "/pts_prev_indices": np.asarray(new_p.pts_prev_indices, dtype=np.int32), name + "/n_pts_fix": np.int64(new_p.n_pts_fix),
+                    name + "/pts3d": new_p.pts3d})
+        print("rm_outliers", name, "obs", p.n_obs, "->", new_p.n_obs, "tracks", p.n_pts, "->", new_p.n_pts, "fixed", p.n_pts_fix, "->",
+              new_p.n_pts_fix, "detected", int(n), "pts3d", new_p.pts3d.dtype, "thr", [float(t) for t in cam_thr], flush=True)
+    save_fixed("rm_outliers", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["fun", "params", "solves", "solves4", "tight2", "tight3", "outliers", "init_pts3d", "rpcfit", "reference_c"]
+    which = sys.argv[1:] or ["fun", "params", "solves", "solves4", "tight2", "tight3", "outliers", "init_pts3d", "rpcfit", "reference_c",
+                             "outliers_edges", "rm_outliers"]
     if "fun" in which:
         golden_fun_and_jac()
     if "params" in which:
@@ -611,3 +699,7 @@ if __name__ == "__main__":
         golden_rpcfit()
     if "reference_c" in which:
         golden_reference_c()
+    if "outliers_edges" in which:
+        golden_outliers_edges()
+    if "rm_outliers" in which:
+        golden_rm_outliers()
