@@ -392,6 +392,34 @@ int satba_rpc_refit(int32_t n_cam, const double *tables_in, const double *rt, co
                     const double *global_transform, int32_t n_samples, double h, double tol, int32_t max_iter, double *tables_out, double *err,
                     double *margins, double *locs_out, double *target_out, int32_t device);
 
+/* ---- cameras from RPCs, the step in front of the path (ba_pipeline.set_cameras / set_camera_centers).  Stand-alone: no problem
+ * handle, float64, all cameras of a call in one launch.  These entries came after satba_version() 5 and left it unchanged: a caller
+ * detects them by their presence in the library (dlsym), not by the version number.
+ * satba_rpc_affine_approx replaces cam_utils.affine_rpc_approx (cam_utils.py:146-174): per camera the first-order expansion of
+ * rpc.projection o ecef_to_latlon_custom at the ECEF point xyz (n_cam x 3; one point per camera), moved to the crop's origin
+ * col0row0 (n_cam x 2): P_out (n_cam x 12, row-major 3 x 4) = [[J, q - J p - (col0, row0)], [0 0 0 1]].
+ * satba_rpc_perspective_approx replaces cam_utils.perspective_rpc_approx / approx_rpc_as_proj_matrix (cam_utils.py:177-198, 234-277):
+ * per camera the n_col x n_row x n_alt mesh (numpy.linspace over col_range / row_range / alt_range, n_cam x 2 each: first and last
+ * sample; columns fastest, altitudes slowest) is localised through the RPC, taken to ECEF and resected.  crop0 (n_cam x 2: col0,
+ * row0): the matrix is moved to the crop's origin and divided by P[2][3] (perspective_rpc_approx); NULL: the matrix as the
+ * resection leaves it (approx_rpc_as_proj_matrix: unit Frobenius norm before the denormalisation, sign arbitrary).  mean_err (n_cam,
+ * may be NULL): mean reprojection error over the mesh in pixels; centers (n_cam x 3, may be NULL): optical centres -M^-1 P[:, 3].
+ * satba_camera_resection replaces cam_utils.camera_matrix (cam_utils.py:309-356, DLT with Hartley's normalisation) for n_cam sets of
+ * n_pts correspondences X (n_cam x n_pts x 3) -> x (n_cam x n_pts x 2).
+ * satba_rpc_mesh is the first phase alone: the ECEF nodes X_out (n_cam x n x 3), their image points x_out (n_cam x n x 2) and
+ * altitudes alt_out (n_cam x n, may be NULL), n = n_col n_row n_alt.
+ * SATBA_E_ARG: a null pointer, a negative count, fewer than 6 correspondences, fewer than 2 samples on an axis, more than 2^20
+ * points per camera.  SATBA_E_NONFINITE: a non-finite input, or points no unique camera fits (a mesh axis of zero extent, coincident
+ * or coplanar points: the second smallest eigenvalue of the DLT normal matrix is below 1e-12 of the largest), or an expansion point
+ * on the polar axis; no output is written then -- a NaN matrix is never returned.  n_cam == 0 returns 0 without a device call. */
+int satba_rpc_affine_approx(int32_t n_cam, const double *tables, const double *xyz, const double *col0row0, double *P_out, int32_t device);
+int satba_rpc_perspective_approx(int32_t n_cam, const double *tables, const double *col_range, const double *row_range,
+                                 const double *alt_range, int32_t n_col, int32_t n_row, int32_t n_alt, const double *crop0, double *P_out,
+                                 double *mean_err, double *centers, int32_t device);
+int satba_camera_resection(int32_t n_cam, int32_t n_pts, const double *X, const double *x, double *P_out, double *mean_err, int32_t device);
+int satba_rpc_mesh(int32_t n_cam, const double *tables, const double *col_range, const double *row_range, const double *alt_range,
+                   int32_t n_col, int32_t n_row, int32_t n_alt, double *X_out, double *x_out, double *alt_out, int32_t device);
+
 /* ---- inspection entry points (parity tests; not used by the solver loop) */
 /* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64): n must equal satba_layout_len */
 enum { SATBA_LAY_PERM = 0, SATBA_LAY_RANK, SATBA_LAY_PT_CNT, SATBA_LAY_SLICE_BASE, SATBA_LAY_E_CAM, SATBA_LAY_OBS_POS, SATBA_LAY_CAM_OFS,

@@ -30,6 +30,7 @@
 #include "satba_tracks.h"
 #include "satba_ftracks.h"
 #include "satba_rpcfit.h"
+#include "satba_camapprox.h"
 #include "satba_schur.h"
 
 #include <dlfcn.h>
@@ -2642,6 +2643,7 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_outliers_api.inc"
 #include "satba_triangulate_api.inc"
 #include "satba_rpcfit_api.inc"
+#include "satba_camapprox_api.inc"
 #include "satba_tracks_api.inc"
 #include "satba_ftracks_api.inc"
 

@@ -33,6 +33,7 @@ SYMBOLS = [
     "satba_solve_lm", "satba_lm_step", "satba_lm_run", "satba_lm_state", "satba_lm_begin", "satba_lm_part", "satba_lm_poll", "satba_profile_linearize", "satba_profile_read", "satba_outliers", "satba_layout_len", "satba_get_layout", "satba_get_info",
     "satba_triangulate_pairwise", "satba_init_pts3d", "satba_init_pts3d_resident", "satba_snapshot_x",
     "satba_rpc_fit", "satba_rpc_localization", "satba_rpc_refit",
+    "satba_rpc_affine_approx", "satba_rpc_perspective_approx", "satba_camera_resection", "satba_rpc_mesh",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
     "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
 ]
@@ -146,6 +147,10 @@ def load_library(path=None):
     lib.satba_rpc_fit.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_int32, _dp, _dp, _ip, C.c_int32]
     lib.satba_rpc_localization.argtypes = [_dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, C.c_int32]
     lib.satba_rpc_refit.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32]
+    lib.satba_rpc_affine_approx.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, C.c_int32]
+    lib.satba_rpc_perspective_approx.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32]
+    lib.satba_camera_resection.argtypes = [C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32]
+    lib.satba_rpc_mesh.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32]
     _fp = C.POINTER(C.c_float)
     lib.satba_triangulate_pairwise.argtypes = [C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _dp, _fp, C.c_int32, _fp]
     lib.satba_init_pts3d.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, C.c_int32, _ip, _fp, _ip,
