@@ -97,24 +97,12 @@ struct satba_problem {
     // (linear loss: bound of a residual) with its copy for the trial point
     double *d_fx = nullptr, *d_bbox = nullptr, *d_fxcost = nullptr, *d_fxcost_new = nullptr, *d_fxcost0 = nullptr;
     int *d_fxflag = nullptr, *d_fxe = nullptr;
-    bool fxcost_valid = false, fxcost_new_valid = false, fxcost0_valid = false;
-    bool decide_fused = false;  // device-resident loop: the next launch_trial carries k_lm_decide1a in its first launch
+    bool fxcost_valid = false, fxcost_new_valid = false, fxcost0_valid = false;  // left by the pass that wrote the cost (or satba_accept), read by the next linearisation / snapshot
     double w_max = 1.0, n_max_cam = 1.0, fx_shrink = 1.0;
     int fx_fallbacks = 0;
-    bool scales_by_tail = false;   // the last queued pattern ended with k_lm_accept_scales and the host has not touched the loop since (lm_launch_tick)
-    bool skip_lin_scales = false;  // ... so this satba_linearize does not launch k_lin_scales
-    // device-resident LM loop (satba_lmdev.h): while a tick is being queued, `gate` points at the word of the loop's state that
-    // switches the kernels of the current part of the pattern on or off, and the trust radius / first-iteration flag / trial
-    // coefficients are read from the state instead of the launch arguments
-    const int* gate = nullptr;
-    const double* Delta_dev = nullptr;
-    const int* first_dev = nullptr;
-    const double* coef_dev = nullptr;
-    int fuse_prep = -1;        // >= 0 while a loop queues a front: k_linearize does the point part of the prepare phase (value: `first`)
-    bool prep_fused = false;   // the linearisation in place did (satba_prepare then only visits the camera entries)
-    const double* lam_force_dev = nullptr;
-    const double* sub_args_dev = nullptr;
-    struct LmDev* d_lm = nullptr;
+    bool scales_by_tail = false;   // left by lm_launch_tail (the pattern ended with k_lm_accept_scales), read by the next lm_launch_tick, cleared by lm_drive
+    bool prep_fused = false;   // left by a linearisation that did the point part of the prepare phase (PhaseCtx::fuse_prep), read by the prepare that follows
+    struct LmDev* d_lm = nullptr;  // device-resident LM loop (satba_lmdev.h)
     struct LmSummary* h_lm = nullptr;  // pinned, mapped: the device posts the progress of the loop here
     struct LmSummary* h_lm_dev = nullptr;
     long long lm_ticks_queued = 0;
@@ -155,10 +143,7 @@ struct satba_problem {
     int* d_fail = nullptr;
     double* d_dinv = nullptr;  // inverted 32 x 32 diagonal blocks of the factor (backward substitution)
     CholWork chol;             // scratch of the tile factorisation (satba_chol3.h)
-    bool scale_in_finish = false;  // front_schur_solve, one rank: k_schur_finish may hand the system over in scaled variables ...
-    bool s_scaled = false;         // ... and has (satba_solve skips k_scale_system)
-    double schur_lam = 0.0;    // damping of the Schur phase being queued (k_schur_finish): value, or where k_vinv left it on the device
-    const double* schur_lam_dev = nullptr;
+    bool s_scaled = false;     // left by k_schur_finish's launcher when it handed the system over in scaled variables (FrontCtx::scale_in_finish), read by the solve
     // the factorisation beside the pair kernel (front_schur_solve): its stream, fork / join events, the producers' counters
     hipStream_t chol_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -166,8 +151,6 @@ struct satba_problem {
     int* d_pair_cnt = nullptr; // weighted / robust runs: chunk items finished per camera pair (SchurArgs::pair_cnt), zero between launches
     int* d_dg_cnt = nullptr;   // ... and diagonal items finished per camera (SchurArgs::dg_cnt)
     long long* d_ts = nullptr; // (tools, -DC3_STAMPS: time stamps of the last factorisation beside the pair kernel, printed when the handle goes)
-    int arrive_epoch = 0;      // != 0 while a front with the factorisation beside it is being queued (launch_schur)
-    bool decide2_fused = false;  // the launch of the trial that is being queued carries the loop's second decision (launch_trial)
     int msg_epoch = 0;         // != 0 between satba_solve_messages_begin and _end: the epoch its factorisation waits for
     double* msg_packed = nullptr;  // the caller's packed payload of that exchange (device-resident loop: parts 10 - 12)
     bool beside_last = false;  // the last front ran that way
@@ -178,7 +161,7 @@ struct satba_problem {
     int beside_timeouts = 0;
     double* d_scal = nullptr;  // 8 private scalars (costs of satba_residuals, timing sinks)
     double* d_keep = nullptr;  // SATBA_KEEP_LEN scalars of the running iteration that outlive the per-phase headers
-    bool prepared = false;
+    bool prepared = false;     // left by the prepare phase, read (and cleared) by satba_schur_auto
     double *d_xb_own = nullptr, *d_xb = nullptr;
     long long xb_len = 0;
     double* h_pin = nullptr;  // pinned staging for header reads
@@ -194,12 +177,31 @@ struct satba_problem {
     double* d_err_keep = nullptr;      // K per-observation errors kept for satba_reprojection_errors_fetch (caller's order)
     hipEvent_t ev_err = nullptr;       // ... complete on the device
     double* d_x0 = nullptr;   // satba_snapshot_x
-    bool linearized = false, have_step = false;
+    bool linearized = false, have_step = false;  // left by the linearisation / the solve, cleared by whatever moves x; read by the phases that need them
     double create_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<void*> allocs;
 
     double* payload() const { return d_xb + hdr; }
     RedBuf red(int slot) const { return RedBuf{d_red + (size_t)slot * RED_MAX_NV * RED_MAX_GRID, d_red_cnt + slot}; }
+};
+// What a caller wants of the phase it queues next.  The default value means "called from outside": nothing gated, nothing fused.
+// The device-resident LM loop (satba_lmdev.h) passes `gate`, the word of its state that switches the kernels of the current part of
+// the pattern on or off, and has the trust radius / first-iteration flag / trial coefficients read from the state (lm_ctx).
+struct PhaseCtx {
+    const int* gate = nullptr;
+    const double *Delta_dev = nullptr, *coef_dev = nullptr, *lam_force_dev = nullptr, *sub_args_dev = nullptr;
+    const int* first_dev = nullptr;
+    int fuse_prep = -1;              // >= 0: k_linearize does the point part of the prepare phase (single-rank loops; value: `first`)
+    bool skip_lin_scales = false;    // the previous tick's k_lm_accept_scales has done k_lin_scales' work (satba_problem::scales_by_tail)
+    bool decide1a_in_trial = false;  // the trial's first launch carries k_lm_decide1a
+    bool decide2_in_trial = false;   // the trial's residual kernel carries the loop's second decision
+};
+// ... and of a Schur phase: the front that queues it (front_schur_solve) and schur_impl fill it in
+struct FrontCtx {
+    int arrive_epoch = 0;          // != 0: the factorisation waits beside this stream (chol_front_launch) for this epoch
+    bool scale_in_finish = false;  // k_schur_finish may hand the system over in scaled variables (the solve follows at once)
+    double lam = 0.0;              // damping (k_schur_finish): value, or where k_vinv left it on the device
+    const double* lam_dev = nullptr;
 };
 // RedBuf slots
 enum { RB_RES = 0, RB_LIN = 1, RB_PREP = 2, RB_JVP = 3, RB_BS = 4, RB_SUB = 5, RB_TRIAL = 6, RB_MISC = 7 };
@@ -254,7 +256,7 @@ static int dev_alloc(satba_problem* p, T** out, size_t count) {
 // weighted / robust runs with recomputed Jacobians (affine, perspective): row scales and point records share the merged records W
 static bool wmode(const satba_problem* p) { return p->model != RPC && !(p->loss == 0 && p->unit_weights); }
 
-static ObsArgs obs_args(const satba_problem* p, bool at_new) {
+static ObsArgs obs_args(const satba_problem* p, bool at_new, const int* gate = nullptr) {
     ObsArgs a;
     const Layout& L = p->L;
     a.e_cam = L.e_cam; a.e_obs = L.e_obs; a.e_w = L.e_w; a.slice_base = L.slice_base; a.pt_cnt = L.pt_cnt; a.perm = L.perm;
@@ -273,7 +275,7 @@ static ObsArgs obs_args(const satba_problem* p, bool at_new) {
     a.f_scale = p->f_scale;
     a.unit = (p->loss == 0 && p->unit_weights) ? 1 : 0;
     a.rep_shift = p->lin_rep_shift;
-    a.fxe = p->d_fxe; a.fx_flag = p->d_fxflag; a.gate = p->gate;
+    a.fxe = p->d_fxe; a.fx_flag = p->d_fxflag; a.gate = gate;
     a.prep_scale = nullptr; a.prep_gh = nullptr; a.prep_ghs = nullptr; a.prep_first_dev = nullptr; a.prep_first = 0;
     a.dir_tab = p->d_dir_tab;
     a.sh = 0;  // lanes per point: set by the launchers of the kernels that support it
@@ -306,7 +308,7 @@ static int raise_lds_limit(K kernel, size_t bytes) {
 
 static int launch_cam_consts(satba_problem* p, bool at_new) {
     hipLaunchKernelGGL(k_cam_consts, dim3((p->M + 63) / 64), dim3(64), 0, p->stream, p->model, p->M, p->NP, p->c_p,
-                       at_new ? p->d_xnew : p->d_x, p->d_cam_static, at_new ? p->d_camc_new : p->d_camc, p->gate);
+                       at_new ? p->d_xnew : p->d_x, p->d_cam_static, at_new ? p->d_camc_new : p->d_camc, (const int*)nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -350,8 +352,8 @@ static int slice_rev(int bit) {
     static const int mask = getenv("SATBA_SLICE_REV") ? atoi(getenv("SATBA_SLICE_REV")) : 1;
     return (mask >> bit) & 1;
 }
-static int launch_residual(satba_problem* p, bool at_new, double2* f, double* cost) {
-    ObsArgs a = obs_args(p, at_new);
+static int launch_residual(satba_problem* p, bool at_new, double2* f, double* cost, const int* gate = nullptr) {
+    ObsArgs a = obs_args(p, at_new, gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(3);
     const int grid = slice_grid(p, RES_THREADS / 64, 2, a.sh);
@@ -366,22 +368,21 @@ static int launch_residual(satba_problem* p, bool at_new, double2* f, double* co
 }
 
 // trial point + cost there + |step|^2, |x|^2 in one pass over the observations (k_residual<..., TRIAL>)
-static int launch_trial(satba_problem* p, double c0, double c1, const double* v0, const double* v1) {
-    if (p->decide_fused) {  // device-resident loop: the decision kernel in front of the trial rides in this launch
-        p->decide_fused = false;
+static int launch_trial(satba_problem* p, const PhaseCtx& c, double c0, double c1, const double* v0, const double* v1) {
+    if (c.decide1a_in_trial) {  // device-resident loop: the decision kernel in front of the trial rides in this launch
         hipLaunchKernelGGL(k_lm_decide1a_trial_cams, dim3(1), dim3(256), 0, p->stream, p->d_lm, p->d_xb, p->model, p->M, p->NP, p->c_p, p->d_x, v0, v1,
                            p->d_scale_inv, p->d_cam_static, p->d_xnew, p->d_camc_new, p->d_xb, (int)p->hdr);
     } else
     hipLaunchKernelGGL(k_trial_cams, dim3((std::max(p->M, (int)p->hdr) + 63) / 64), dim3(64), 0, p->stream, p->model, p->M, p->NP, p->c_p, p->d_x, v0, v1,
-                       p->d_scale_inv, c0, c1, p->d_cam_static, p->d_xnew, p->d_camc_new, p->d_xb, (int)p->hdr, p->coef_dev, p->gate);
+                       p->d_scale_inv, c0, c1, p->d_cam_static, p->d_xnew, p->d_camc_new, p->d_xb, (int)p->hdr, c.coef_dev, c.gate);
     HIP_TRY(hipGetLastError());
-    ObsArgs a = obs_args(p, true);
+    ObsArgs a = obs_args(p, true, c.gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(3);
     const int grid = slice_grid(p, RES_THREADS / 64, 2, a.sh);
     const size_t lds = table_bytes(p);
-    TrialArgs t{p->d_x, v0, v1, p->d_scale_inv, p->d_xnew, c0, c1, p->lead, p->d_xb + 2, p->d_xb + 3, p->d_fxcost_new, p->coef_dev};
-    if (p->decide2_fused) { t.lm_st = p->d_lm; t.lm_sum = p->h_lm_dev; }  // (lm_launch_tail: one rank, device-resident loop)
+    TrialArgs t{p->d_x, v0, v1, p->d_scale_inv, p->d_xnew, c0, c1, p->lead, p->d_xb + 2, p->d_xb + 3, p->d_fxcost_new, c.coef_dev};
+    if (c.decide2_in_trial) { t.lm_st = p->d_lm; t.lm_sum = p->h_lm_dev; }  // (lm_launch_tail: one rank, device-resident loop)
     p->fxcost_new_valid = true;
     double* cost = p->d_xb + 1;
     if (p->loss == 0 && p->unit_weights)
@@ -453,13 +454,13 @@ static int raise_lin_limits(satba_problem* p) {
     return 0;
 }
 
-static int launch_linearize_kernel(satba_problem* p) {
-    ObsArgs a = obs_args(p, false);
+static int launch_linearize_kernel(satba_problem* p, const PhaseCtx& c) {
+    ObsArgs a = obs_args(p, false, c.gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(0);
-    if (p->fuse_prep >= 0) {  // single-rank loops: the point part of the prepare phase rides in this kernel
+    if (c.fuse_prep >= 0) {  // single-rank loops: the point part of the prepare phase rides in this kernel
         a.prep_scale = p->d_scale_inv; a.prep_gh = p->d_gh; a.prep_ghs = p->d_q1;
-        a.prep_first = p->fuse_prep; a.prep_first_dev = p->first_dev;
+        a.prep_first = c.fuse_prep; a.prep_first_dev = c.first_dev;
     }
     const bool prof = p->prof_lin && p->prof_used + 2 <= 2 * 4096;
     if (prof) {
@@ -479,13 +480,13 @@ static int launch_linearize_kernel(satba_problem* p) {
 }
 
 // camera-major camera sums of the stored linearisation -> U (full blocks), g_c
-static int launch_cam_sums(satba_problem* p, double* U, double* gc) {
-    ObsArgs a = obs_args(p, false);
+static int launch_cam_sums(satba_problem* p, const int* gate, double* U, double* gc) {
+    ObsArgs a = obs_args(p, false, gate);
     CamMajor cm = cam_major(p);
     SATBA_DISPATCH(p, hipLaunchKernelGGL((k_cam_sums<MODEL, NP>), dim3(p->M, p->cm_chunks), dim3(LINC_THREADS), 0, p->stream, a, cm, p->d_f, p->d_part3));
     HIP_TRY(hipGetLastError());
     const int total = p->M * cam_acc_len(p->NP);
-    hipLaunchKernelGGL(k_cam_sums_finish, dim3((total + 255) / 256), dim3(256), 0, p->stream, p->M, p->NP, p->cm_chunks, p->d_part3, U, gc, p->gate);
+    hipLaunchKernelGGL(k_cam_sums_finish, dim3((total + 255) / 256), dim3(256), 0, p->stream, p->M, p->NP, p->cm_chunks, p->d_part3, U, gc, gate);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -504,7 +505,7 @@ static SchurArgs schur_args(const satba_problem* p) {
 }
 
 template <int MODEL, int NP>
-static int launch_schur(satba_problem* p, const ObsArgs& a, double* S, double* rhs) {
+static int launch_schur(satba_problem* p, const FrontCtx& f, const ObsArgs& a, double* S, double* rhs) {
     CamMajor cm = cam_major(p);
     SchurArgs s = schur_args(p);
     const long long n_pairs = p->L.n_pairs;
@@ -515,7 +516,7 @@ static int launch_schur(satba_problem* p, const ObsArgs& a, double* S, double* r
     int dchunks = (a.sc && MODEL != RPC) ? p->cm_chunks_w : p->cm_chunks;
     // the factorisation BEHIND the Schur kernels (no arrival protocol): the diagonal pass and the pair kernel in one launch (k_schur_both)
     static const bool one_launch_env = !(getenv("SATBA_SCHUR_ONE_LAUNCH") && atoi(getenv("SATBA_SCHUR_ONE_LAUNCH")) == 0);
-    const bool both = one_launch_env && !p->arrive_epoch && !dg_in_pairs && pairs_run;
+    const bool both = one_launch_env && !f.arrive_epoch && !dg_in_pairs && pairs_run;
     if (dg_in_pairs) dchunks = p->L.n_dg;
     else {
         if (s.wmode) cm.pt = p->L.cm_rec;  // (k_schur_diag on the merged records: piece offsets instead of point indices)
@@ -527,23 +528,23 @@ static int launch_schur(satba_problem* p, const ObsArgs& a, double* S, double* r
     // end of the phase: diagonal blocks, right-hand side, header (and the pairs' chunk partials, red_chunks > 1) in one launch
     auto finish = [&](int red_chunks, bool direct) {  // direct: the pair kernel writes (has written) blocks of S itself
         const long long outs = red_chunks > 1 ? n_pairs * NP * NP : 0;
-        const bool scale = p->scale_in_finish && !direct && 1 + CH_MAX_STEPS <= nb_diag * 256;
+        const bool scale = f.scale_in_finish && !direct && 1 + CH_MAX_STEPS <= nb_diag * 256;
         hipLaunchKernelGGL(k_schur_finish, dim3((unsigned)(nb_diag + (outs + 255) / 256)), dim3(256), 0, p->stream, p->M, NP, p->n_c, dchunks, p->d_part3,
-                           p->schur_lam, p->schur_lam_dev, p->lead, p->d_gc, p->d_scale_inv, S, rhs, p->d_xb, (int)p->hdr, nb_diag, red_chunks,
-                           p->L.pair_ij, p->d_pair_part, p->gate, scale ? p->d_dch : (double*)nullptr, scale ? p->d_fail : (int*)nullptr,
+                           f.lam, f.lam_dev, p->lead, p->d_gc, p->d_scale_inv, S, rhs, p->d_xb, (int)p->hdr, nb_diag, red_chunks,
+                           p->L.pair_ij, p->d_pair_part, a.gate, scale ? p->d_dch : (double*)nullptr, scale ? p->d_fail : (int*)nullptr,
                            scale ? 1 + CH_MAX_STEPS : 0);
         p->s_scaled = scale;
     };
-    if (p->arrive_epoch) {  // the factorisation waits beside this stream: diagonal blocks and right-hand side first, the pair kernel counts its items in
+    if (f.arrive_epoch) {  // the factorisation waits beside this stream: diagonal blocks and right-hand side first, the pair kernel counts its items in
         if (dg_in_pairs) {  // ... or they come out of the pair kernel as well (SchurArgs::dg_cnt): only the header is cleared here
             const int keep = dchunks;
             dchunks = 0;
             finish(1, true);
             dchunks = keep;
-            s.dg_cnt = p->d_dg_cnt; s.dg_lam = p->schur_lam; s.dg_lam_dev = p->schur_lam_dev; s.dg_lead = p->lead; s.dg_gc = p->d_gc;
+            s.dg_cnt = p->d_dg_cnt; s.dg_lam = f.lam; s.dg_lam_dev = f.lam_dev; s.dg_lead = p->lead; s.dg_gc = p->d_gc;
             s.dg_scale_inv = p->d_scale_inv; s.dg_rhs = rhs;
         } else finish(1, true);
-        s.arrive = p->d_arrive; s.arrive_epoch = p->arrive_epoch; s.pair_cnt = p->d_pair_cnt; s.fail = p->d_fail;
+        s.arrive = p->d_arrive; s.arrive_epoch = f.arrive_epoch; s.pair_cnt = p->d_pair_cnt; s.fail = p->d_fail;
     }
     int red_chunks = 1;
     if (n_pairs > 0 && p->L.E > 0) {
@@ -560,23 +561,23 @@ static int launch_schur(satba_problem* p, const ObsArgs& a, double* S, double* r
         else hipLaunchKernelGGL((k_schur_pairs<MODEL, NP, false>), igrid, dim3(256), 0, p->stream, a, s, S);
         HIP_TRY(hipGetLastError());
         if (p->L.C > 1 && !merged) red_chunks = p->L.C;
-        if (p->arrive_epoch && (a.unit ? red_chunks > 1 : false)) return fail(SATBA_E_STATE, "factorisation beside a unit-weight pair kernel with chunk partials");
+        if (f.arrive_epoch && (a.unit ? red_chunks > 1 : false)) return fail(SATBA_E_STATE, "factorisation beside a unit-weight pair kernel with chunk partials");
     }
-    if (!p->arrive_epoch) finish(red_chunks, n_pairs > 0 && p->L.E > 0 && red_chunks == 1);
+    if (!f.arrive_epoch) finish(red_chunks, n_pairs > 0 && p->L.E > 0 && red_chunks == 1);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-static int launch_schur_kernel(satba_problem* p) {
-    ObsArgs a = obs_args(p, false);
+static int launch_schur_kernel(satba_problem* p, const int* gate, const FrontCtx& f) {
+    ObsArgs a = obs_args(p, false, gate);
     double* S = p->payload();
     double* rhs = S + (size_t)p->n_c * p->n_c;
-    SATBA_DISPATCH(p, TRY((launch_schur<MODEL, NP>(p, a, S, rhs))));
+    SATBA_DISPATCH(p, TRY((launch_schur<MODEL, NP>(p, f, a, S, rhs))));
     return 0;
 }
 
-static int launch_backsub_kernel(satba_problem* p) {
-    ObsArgs a = obs_args(p, false);
+static int launch_backsub_kernel(satba_problem* p, const int* gate) {
+    ObsArgs a = obs_args(p, false, gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(1);
     const int grid = slice_grid(p, BS_THREADS / 64, 2, a.sh);
@@ -595,8 +596,8 @@ static int launch_backsub_kernel(satba_problem* p) {
 }
 
 // pre: q1 is already in unscaled variables (nv == 1 only)
-static int launch_jvp(satba_problem* p, int nv, const double* q1, const double* q2, double* out, bool pre = false) {
-    ObsArgs a = obs_args(p, false);
+static int launch_jvp(satba_problem* p, const int* gate, int nv, const double* q1, const double* q2, double* out, bool pre = false) {
+    ObsArgs a = obs_args(p, false, gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(2);
     const int grid = slice_grid(p, JVP_THREADS / 64, 2, a.sh);
@@ -624,11 +625,11 @@ static int launch_jvp(satba_problem* p, int nv, const double* q1, const double* 
 
 // S z = rhs for the reduced system (S column-major lower, destroyed; b in place)
 // unscaled (or null): set to whether the step in unscaled variables and the phase's header were written as well (k_unscale's work)
-static int dense_solve(satba_problem* p, double* S, double* b, bool cleared = false, bool* unscaled = nullptr) {
+static int dense_solve(satba_problem* p, const int* gate, double* S, double* b, bool cleared = false, bool* unscaled = nullptr) {
     TrsvTail tail;
     tail.dc = p->d_dc; tail.scale_inv = p->d_scale_inv; tail.hdr = p->d_xb; tail.hdr_len = (int)p->hdr; tail.fail = p->d_fail; tail.lead = p->lead;
     tail.keep = p->d_keep; tail.keep_at = SATBA_HDR_KEEP; tail.keep_len = SATBA_KEEP_LEN;
-    const bool done = cholesky_solve(S, p->n_c, b, p->d_fail, p->d_fail + 1, p->stream, p->chol, p->d_dinv, cleared, p->gate, nullptr,
+    const bool done = cholesky_solve(S, p->n_c, b, p->d_fail, p->d_fail + 1, p->stream, p->chol, p->d_dinv, cleared, gate, nullptr,
                                      unscaled ? &tail : nullptr);  // clears d_fail and the flags unless the caller has
     if (unscaled) *unscaled = done;
     HIP_TRY(hipGetLastError());
@@ -1466,10 +1467,10 @@ int satba_residuals(satba_problem* p, double* host_r, double* host_cost) {
     return 0;
 }
 
-int satba_linearize(satba_problem* p) {
+// ---- the phases as the loops below queue them: a context per call, the state checks of the ABI (a loop may be driven from outside
+// part by part: satba_lm_part), the range marker; the public entry points add the handle check and the device
+static int linearize_impl(satba_problem* p, const PhaseCtx& c) {
     Range range_("satba:linearize");
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(p->device));
     TRY(ensure_wlayout(p));
     const size_t nU = (size_t)p->M * p->NP * p->NP;
     const int n_clear = (int)(p->hdr + nU + p->n_c);  // header, U (only its diagonal is written), g_c
@@ -1477,17 +1478,17 @@ int satba_linearize(satba_problem* p) {
         // scales of the fixed-point camera sums: the linear loss bounds a residual by sqrt(2 cost(x)) -- the cost of the trial
         // evaluation that led here (satba_accept), else one cost-only pass
         if (p->loss == 0 && !p->fxcost_valid) {
-            TRY(launch_residual(p, false, nullptr, p->d_fxcost));
+            TRY(launch_residual(p, false, nullptr, p->d_fxcost, c.gate));
             p->fxcost_valid = true;
         }
-        if (!p->skip_lin_scales)  // (device-resident loop on one rank: the previous tick's k_lm_accept_scales has done it)
+        if (!c.skip_lin_scales)  // (device-resident loop on one rank: the previous tick's k_lm_accept_scales has done it)
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_lin_scales<MODEL, NP>), dim3(1), dim3(256), 0, p->stream, p->M, p->d_camc, p->d_rpc, p->d_bbox, p->w_max,
-                                             p->loss, p->f_scale, p->d_fxcost, p->n_max_cam, p->fx_shrink, p->d_fx, p->d_fxe, p->d_fxflag, p->d_xb, n_clear, p->gate));
+                                             p->loss, p->f_scale, p->d_fxcost, p->n_max_cam, p->fx_shrink, p->d_fx, p->d_fxe, p->d_fxflag, p->d_xb, n_clear, c.gate));
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemsetAsync(p->d_xb, 0, sizeof(double) * n_clear, p->stream));
     }
-    TRY(launch_linearize_kernel(p));
+    TRY(launch_linearize_kernel(p, c));
     double* U = p->payload();
     double* gc = U + nU;
     if (p->cam_sums_lds) {
@@ -1496,48 +1497,58 @@ int satba_linearize(satba_problem* p) {
         const int const_t = lin_const_t(p->model, p->NP, p->loss != 0, p->loss == 0 && p->unit_weights) && lin_variant(p) == 0;
         const int total = p->M * 2 * p->NP;
         hipLaunchKernelGGL(k_lin_finish, dim3((total + 63) / 64), dim3(1024), 0, p->stream, p->M, p->NP, p->lin_grid, p->d_part, U, gc,
-                           p->L.cam_ofs, p->d_camc, p->n_cam_fix, const_t, p->d_fx, p->d_fxe, p->d_fxflag, p->d_xb + SATBA_HDR_FX, p->gate);
+                           p->L.cam_ofs, p->d_camc, p->n_cam_fix, const_t, p->d_fx, p->d_fxe, p->d_fxflag, p->d_xb + SATBA_HDR_FX, c.gate);
         HIP_TRY(hipGetLastError());
     } else {
-        TRY(launch_cam_sums(p, U, gc));  // camera-major pass, fixed summation order; fills the full blocks
+        TRY(launch_cam_sums(p, c.gate, U, gc));  // camera-major pass, fixed summation order; fills the full blocks
     }
     p->linearized = true; p->have_step = false;
     p->f_valid = !p->cam_sums_lds && p->model == RPC;
-    p->prep_fused = p->fuse_prep >= 0;
+    p->prep_fused = c.fuse_prep >= 0;
     return 0;
 }
-
-int satba_prepare(satba_problem* p, int32_t first) {
-    Range range_("satba:prepare");
+int satba_linearize(satba_problem* p) {
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->linearized) return fail(SATBA_E_STATE, "prepare before linearize");
     HIP_TRY(hipSetDevice(p->device));
+    return linearize_impl(p, PhaseCtx{});
+}
+
+static int prepare_impl(satba_problem* p, const PhaseCtx& c, int first) {
+    Range range_("satba:prepare");
+    if (!p->linearized) return fail(SATBA_E_STATE, "prepare before linearize");
     const size_t nU = (size_t)p->M * p->NP * p->NP;
     if (p->hdr > 1024) return fail(SATBA_E_ARG, "header too long");
     if (p->prep_fused && p->n_c <= 1024) {  // the point entries are done (k_linearize): stash and camera entries in one launch
         hipLaunchKernelGGL(k_prepare_cams, dim3(1), dim3(1024), 0, p->stream, (int)nU, p->n_c, p->NP, p->world, SATBA_HDR_FIXED, (int)p->hdr, first, p->lead,
-                           p->d_xb, p->d_U, p->d_gc, p->d_keep, p->d_x, p->d_g, p->d_scale_inv, p->d_gh, p->d_q1, p->first_dev, p->gate);
+                           p->d_xb, p->d_U, p->d_gc, p->d_keep, p->d_x, p->d_g, p->d_scale_inv, p->d_gh, p->d_q1, c.first_dev, c.gate);
         HIP_TRY(hipGetLastError());
-        TRY(launch_jvp(p, 1, p->d_q1, p->d_q1, p->d_xb + 2, true));  // d_q1 is free until the subspace phase
+        TRY(launch_jvp(p, c.gate, 1, p->d_q1, p->d_q1, p->d_xb + 2, true));  // d_q1 is free until the subspace phase
         p->prepared = true;
         return 0;
     }
     hipLaunchKernelGGL(k_prepare_stash, dim3(1), dim3(1024), 0, p->stream, (int)nU, p->n_c, p->world, SATBA_HDR_FIXED, (int)p->hdr, p->d_xb, p->d_U,
-                       p->d_gc, p->d_keep, p->gate);
+                       p->d_gc, p->d_keep, c.gate);
     HIP_TRY(hipGetLastError());
     const int n_prep = p->prep_fused ? p->n_c : p->n;  // fused: the point entries are done
     hipLaunchKernelGGL(k_prepare_vec, dim3(grid_for(n_prep, 256, 1024)),  // measured at 3 M entries: 512 workgroups 51 us, 1024: 45, 2048: 55
                        dim3(256), 0, p->stream, n_prep, p->n_c, p->NP, first,
-                       p->lead, p->d_U, p->d_gc, p->d_V, p->d_x, p->d_g, p->d_scale_inv, p->d_gh, p->d_q1, p->red(RB_PREP), p->d_xb, p->d_keep, p->first_dev, p->gate);
+                       p->lead, p->d_U, p->d_gc, p->d_V, p->d_x, p->d_g, p->d_scale_inv, p->d_gh, p->d_q1, p->red(RB_PREP), p->d_xb, p->d_keep, c.first_dev, c.gate);
     HIP_TRY(hipGetLastError());
-    TRY(launch_jvp(p, 1, p->d_q1, p->d_q1, p->d_xb + 2, true));  // d_q1 is free until the subspace phase
+    TRY(launch_jvp(p, c.gate, 1, p->d_q1, p->d_q1, p->d_xb + 2, true));  // d_q1 is free until the subspace phase
     p->prepared = true;
     return 0;
 }
+int satba_prepare(satba_problem* p, int32_t first) {
+    if (!p) return fail(SATBA_E_ARG, "null handle");
+    HIP_TRY(hipSetDevice(p->device));
+    return prepare_impl(p, PhaseCtx{}, first);
+}
 
-// automatic: the damping comes from the prepare header and the trust radius Delta (satba_schur_auto)
-static int schur_impl(satba_problem* p, double lam, bool automatic, double Delta, double lam_floor) {
+// automatic: the damping comes from the prepare header and the trust radius Delta (satba_schur_auto), which consumes the prepare header
+static int schur_impl(satba_problem* p, const PhaseCtx& c, FrontCtx f, double lam, bool automatic, double Delta, double lam_floor) {
     Range range_("satba:schur");
+    if (!p->linearized || (automatic && !p->prepared)) return fail(SATBA_E_STATE, automatic ? "schur_auto before prepare" : "schur before linearize");
+    if (automatic) p->prepared = false;
     const size_t nS = (size_t)p->n_c * p->n_c + p->n_c;
     const bool pairs_run = p->L.n_pairs > 0 && p->L.E > 0;
     const double* lam_dev = automatic ? p->d_keep + 5 : nullptr;
@@ -1545,19 +1556,18 @@ static int schur_impl(satba_problem* p, double lam, bool automatic, double Delta
         const bool w = wmode(p) && p->L.wl_ready;  // the records go into the merged records W, behind the row scales k_linearize left there
         hipLaunchKernelGGL(k_vinv, dim3((p->N + VINV_THREADS - 1) / VINV_THREADS), dim3(VINV_THREADS), 0, p->stream, p->N, lam, automatic ? p->d_xb : nullptr, Delta, lam_floor,
                            p->d_keep, p->d_V, p->d_scale_inv + p->n_c, p->d_Vinv, p->d_x + p->n_c, p->d_g + p->n_c, w ? reinterpret_cast<double*>(p->d_W) : p->d_PV,
-                           p->L.perm, p->n_pts_fix, automatic ? p->Delta_dev : nullptr, automatic ? p->lam_force_dev : nullptr, p->gate,
+                           p->L.perm, p->n_pts_fix, automatic ? c.Delta_dev : nullptr, automatic ? c.lam_force_dev : nullptr, c.gate,
                            w ? p->L.w_fix : (const int*)nullptr);
     } else if (automatic) {
-        hipLaunchKernelGGL(k_lambda, dim3(1), dim3(1), 0, p->stream, p->d_xb, Delta, lam_floor, p->d_keep, p->Delta_dev, p->lam_force_dev, p->gate);
+        hipLaunchKernelGGL(k_lambda, dim3(1), dim3(1), 0, p->stream, p->d_xb, Delta, lam_floor, p->d_keep, c.Delta_dev, c.lam_force_dev, c.gate);
     }
     HIP_TRY(hipGetLastError());
     // The header is cleared by k_schur_finish (k_vinv reads it).  S and rhs are only cleared when no pair kernel will run: every block
     // of the lower triangle is otherwise written by the kernels below (k_schur_finish the diagonal blocks and rhs, the pair kernel or
     // k_schur_finish every off-diagonal block).
     if (!pairs_run) HIP_TRY(hipMemsetAsync(p->d_xb + p->hdr, 0, sizeof(double) * nS, p->stream));
-    p->schur_lam = lam; p->schur_lam_dev = lam_dev;
-    TRY(launch_schur_kernel(p));
-    return 0;
+    f.lam = lam; f.lam_dev = lam_dev;
+    return launch_schur_kernel(p, c.gate, f);
 }
 
 // schur (+ auto damping) and solve of a front
@@ -1579,7 +1589,6 @@ static bool chol_beside_ok(const satba_problem* p) {
     return p->world == 1 && items_ok && p->L.n_pairs > 0 && p->L.E > 0 && p->n_c == p->M * p->NP && p->n_c > 128 && p->n_c <= 1024 && p->N > 0 &&
            !p->beside_off;
 }
-static int front_schur_solve(satba_problem* p, bool automatic, double lam, double Delta, double lam_floor);
 // header slot 4 of the solve phase = lead x status word of the factorisation: bit 1 = a wait timed out.  Beside the pair kernel that
 // means the two kernels did not run at the same time (a profiler collecting counters serialises the launches): the handle goes back
 // to one kernel after the other and the caller repeats the front with the same damping.
@@ -1618,9 +1627,9 @@ static int chol_front_streams(satba_problem* p) {
     HIP_TRY(hipMemsetAsync(p->d_dg_cnt, 0, sizeof(int) * (size_t)p->M, p->stream));
     return 0;
 }
-// k_chol_tiles (wgs workgroups) and the backward substitution on the other stream, behind everything queued on p->stream so far; leaves
-// the launch's epoch in p->arrive_epoch.  arr_extra: C3Args::arr_extra.
-static int chol_front_launch(satba_problem* p, int wgs, int arr_extra, long long arr_timeout) {
+// k_chol_tiles (wgs workgroups) and the backward substitution on the other stream, behind everything queued on p->stream so far; *epoch:
+// the launch's epoch (FrontCtx::arrive_epoch, chol_front_finish).  arr_extra: C3Args::arr_extra.
+static int chol_front_launch(satba_problem* p, const int* gate, int wgs, int arr_extra, long long arr_timeout, int* epoch) {
     Range range_("satba:solve");
     double* S = p->payload();
     double* rhs = S + (size_t)p->n_c * p->n_c;
@@ -1640,39 +1649,38 @@ static int chol_front_launch(satba_problem* p, int wgs, int arr_extra, long long
     g.arrive = p->d_arrive; g.arr_M = p->M; g.np = p->NP; g.arr_epoch = g.epoch; g.si = p->d_scale_inv; g.rhs = rhs;
     g.arr_extra = arr_extra;
     g.arr_timeout = arr_timeout;
-    hipLaunchKernelGGL(k_chol_tiles, dim3(std::min(chol_tiles_grid(n, 1), wgs)), dim3(1024), c3_lds_bytes(), p->chol_stream, g, p->gate);
+    hipLaunchKernelGGL(k_chol_tiles, dim3(std::min(chol_tiles_grid(n, 1), wgs)), dim3(1024), c3_lds_bytes(), p->chol_stream, g, gate);
     hipLaunchKernelGGL(k_trsv_back_mw, dim3((n + CH_SB - 1) / CH_SB), dim3(512), 0, p->chol_stream, S, p->d_dinv, n, p->d_dch,
-                       p->d_fail + 1 + CH_TRSV_FLAGS, p->gate, p->d_arrive + (size_t)SCHUR_ARRIVE_STRIDE * (p->M + 1), g.epoch);
+                       p->d_fail + 1 + CH_TRSV_FLAGS, gate, p->d_arrive + (size_t)SCHUR_ARRIVE_STRIDE * (p->M + 1), g.epoch);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(p->ev_join, p->chol_stream));
-    p->arrive_epoch = g.epoch;
+    *epoch = g.epoch;
     return 0;
 }
 // the rest of the solve phase on p->stream: k_unscale waits for the word the backward substitution posts on the other stream (the event
 // only orders what follows), then the points' part of the step
-static int chol_front_finish(satba_problem* p, int epoch) {
+static int chol_front_finish(satba_problem* p, const int* gate, int epoch) {
     const int nu = std::max(p->n_c, (int)p->hdr);
     hipLaunchKernelGGL(k_unscale, dim3((nu + 255) / 256), dim3(256), 0, p->stream, p->n_c, p->d_scale_inv, p->d_dch, p->d_dc, (int)p->hdr,
-                       p->d_xb, p->d_fail, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, p->gate,
+                       p->d_xb, p->d_fail, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, gate,
                        p->d_arrive + (size_t)SCHUR_ARRIVE_STRIDE * (p->M + 1), epoch);
     HIP_TRY(hipGetLastError());
-    TRY(launch_backsub_kernel(p));
+    TRY(launch_backsub_kernel(p, gate));
     HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_join, 0));
     p->have_step = true;
     return 0;
 }
 
-static int front_schur_solve(satba_problem* p, bool automatic, double lam, double Delta, double lam_floor) {
+static int solve_impl(satba_problem* p, const PhaseCtx& c);
+static int front_schur_solve(satba_problem* p, const PhaseCtx& c, bool automatic, double lam, double Delta, double lam_floor) {
+    FrontCtx f;
     if (p->beside_off && ++p->beside_clean > p->beside_retry_after) p->beside_off = false;  // (chol_beside_ok decides whether it applies at all)
     p->beside_last = chol_beside_ok(p);
     if (!p->beside_last) {
-        p->scale_in_finish = p->world == 1 && p->n_c > CH_ONE_LAUNCH;  // (the solve follows at once: nobody looks at S in between)
-        const int rc = automatic ? satba_schur_auto(p, Delta, lam_floor) : satba_schur(p, lam);
-        p->scale_in_finish = false;
-        if (rc) { p->s_scaled = false; return rc; }
-        return satba_solve(p);
+        f.scale_in_finish = p->world == 1 && p->n_c > CH_ONE_LAUNCH;  // (the solve follows at once: nobody looks at S in between)
+        if (const int rc = schur_impl(p, c, f, lam, automatic, Delta, lam_floor)) { p->s_scaled = false; return rc; }
+        return solve_impl(p, c);
     }
-    HIP_TRY(hipSetDevice(p->device));
     TRY(chol_front_streams(p));
     const char* env_wgs = getenv("SATBA_CHOL_BESIDE_WGS");
     // workgroups (= CUs) lent to the factorisation, a multiple of the eight XCDs.  Measured at 200 cameras x 5 (round 5, LM it/s): beside the
@@ -1684,15 +1692,12 @@ static int front_schur_solve(satba_problem* p, bool automatic, double lam, doubl
     // 5 ms + ~10 x what the kernels in front of a tile's last producer take at HBM speed (hit lists and records: ~100 bytes per hit)
     const long long timeout = 500000 + (long long)((double)p->L.E * 100.0 / 6e12 * 1e8 * 10.0) + (long long)((double)p->K * 200.0 / 6e12 * 1e8 * 10.0);
     // (the pair kernel of the weighted / robust runs writes the diagonal blocks and the right-hand side, too: launch_schur)
-    TRY(chol_front_launch(p, wgs, weighted_front ? 1 : 0, timeout));
-    const int epoch = p->arrive_epoch;
-    const int rc = automatic ? satba_schur_auto(p, Delta, lam_floor) : satba_schur(p, lam);
-    p->arrive_epoch = 0;
-    if (rc) {
+    TRY(chol_front_launch(p, c.gate, wgs, weighted_front ? 1 : 0, timeout, &f.arrive_epoch));
+    if (const int rc = schur_impl(p, c, f, lam, automatic, Delta, lam_floor)) {
         HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_join, 0));  // (the other stream's work is bounded by its time-out)
         return rc;
     }
-    return chol_front_finish(p, epoch);
+    return chol_front_finish(p, c.gate, f.arrive_epoch);
 }
 
 // ---- several ranks: the all-reduce of S in messages, the factorisation beside it (round 6).  The packed payload
@@ -1735,35 +1740,40 @@ int32_t satba_solve_messages(satba_problem* p, int64_t* bounds, int32_t cap) {
     return nm;
 }
 // pack S | rhs | header into `packed` and launch the factorisation, which waits for the messages
-int satba_solve_messages_begin(satba_problem* p, double* packed, int32_t packed_already) {
-    if (!p || !packed) return fail(SATBA_E_ARG, "null argument");
+static int solve_messages_begin_impl(satba_problem* p, const int* gate, double* packed, int packed_already) {
+    if (!packed) return fail(SATBA_E_ARG, "null argument");
     if (!solve_messages_ok(p)) return fail(SATBA_E_ARG, "the reduced system of this handle is solved in one piece (satba_solve)");
-    HIP_TRY(hipSetDevice(p->device));
     TRY(chol_front_streams(p));
-    if (!packed_already) hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, packed, 0, 0, p->n_c, p->gate);
+    if (!packed_already) hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, packed, 0, 0, p->n_c, gate);
     HIP_TRY(hipGetLastError());
     // a message is a collective of the caller's library between host-side calls: the wait is sized for those, not for a kernel (2 s;
     // SATBA_PIPELINE_TIMEOUT_MS); a time-out is reported like any failed factorisation
     static const long long ms = getenv("SATBA_PIPELINE_TIMEOUT_MS") ? atoll(getenv("SATBA_PIPELINE_TIMEOUT_MS")) : 2000;
     static const int wgs = getenv("SATBA_PIPELINE_WGS") ? std::max(8, atoi(getenv("SATBA_PIPELINE_WGS"))) : 64;
-    TRY(chol_front_launch(p, wgs, 0, ms * 100000));
-    p->msg_epoch = p->arrive_epoch;
-    p->arrive_epoch = 0;  // (no Schur kernel of this rank is a producer)
-    return 0;
+    return chol_front_launch(p, gate, wgs, 0, ms * 100000, &p->msg_epoch);  // (no Schur kernel of this rank is a producer: no FrontCtx)
+}
+int satba_solve_messages_begin(satba_problem* p, double* packed, int32_t packed_already) {
+    if (!p) return fail(SATBA_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    return solve_messages_begin_impl(p, nullptr, packed, packed_already);
 }
 // message m has been all-reduced in `packed`: its columns into S (message 0: header and right-hand side, too), its cameras counted in
-int satba_solve_messages_arrived(satba_problem* p, const double* packed, int32_t m) {
-    if (!p || !packed) return fail(SATBA_E_ARG, "null argument");
+static int solve_messages_arrived_impl(satba_problem* p, const int* gate, const double* packed, int m) {
+    if (!packed) return fail(SATBA_E_ARG, "null argument");
     std::vector<int> cb;
     const int nm = schur_message_cams(p, cb);
     if (m < 0 || m >= nm || !p->msg_epoch) return fail(SATBA_E_STATE, "no such message, or no satba_solve_messages_begin");
-    HIP_TRY(hipSetDevice(p->device));
     const int c_lo = cb[m] * p->NP, c_hi = cb[m + 1] * p->NP;
-    hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, const_cast<double*>(packed), 1, c_lo, c_hi, p->gate);
+    hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, const_cast<double*>(packed), 1, c_lo, c_hi, gate);
     hipLaunchKernelGGL(k_mark_arrived, dim3((cb[m + 1] - cb[m] + 63) / 64), dim3(64), 0, p->stream, p->d_arrive, cb[m], cb[m + 1], p->M, p->msg_epoch, m == 0 ? 1 : 0,
-                       p->gate);
+                       gate);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+int satba_solve_messages_arrived(satba_problem* p, const double* packed, int32_t m) {
+    if (!p) return fail(SATBA_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    return solve_messages_arrived_impl(p, nullptr, packed, m);
 }
 // the packed payload the device-resident loop's parts 10 - 12 work on (satba_lm_part has no pointer argument)
 int satba_solve_messages_bind(satba_problem* p, double* packed) {
@@ -1771,102 +1781,105 @@ int satba_solve_messages_bind(satba_problem* p, double* packed) {
     p->msg_packed = packed;
     return 0;
 }
-int satba_solve_messages_end(satba_problem* p) {
-    if (!p) return fail(SATBA_E_ARG, "null handle");
+static int solve_messages_end_impl(satba_problem* p, const int* gate) {
     if (!p->msg_epoch) return fail(SATBA_E_STATE, "satba_solve_messages_end before _begin");
-    HIP_TRY(hipSetDevice(p->device));
     const int epoch = p->msg_epoch;
     p->msg_epoch = 0;
-    return chol_front_finish(p, epoch);
+    return chol_front_finish(p, gate, epoch);
+}
+int satba_solve_messages_end(satba_problem* p) {
+    if (!p) return fail(SATBA_E_ARG, "null handle");
+    HIP_TRY(hipSetDevice(p->device));
+    return solve_messages_end_impl(p, nullptr);
 }
 
 int satba_schur(satba_problem* p, double lam) {
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->linearized) return fail(SATBA_E_STATE, "schur before linearize");
     HIP_TRY(hipSetDevice(p->device));
-    return schur_impl(p, lam, false, 0.0, 0.0);
+    return schur_impl(p, PhaseCtx{}, FrontCtx{}, lam, false, 0.0, 0.0);
 }
-
 int satba_schur_auto(satba_problem* p, double Delta, double lam_floor) {
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->linearized || !p->prepared) return fail(SATBA_E_STATE, "schur_auto before prepare");
     HIP_TRY(hipSetDevice(p->device));
-    p->prepared = false;  // the prepare header is gone after this call
-    return schur_impl(p, 0.0, true, Delta, lam_floor);
+    return schur_impl(p, PhaseCtx{}, FrontCtx{}, 0.0, true, Delta, lam_floor);
 }
 
-int satba_solve(satba_problem* p) {
+static int solve_impl(satba_problem* p, const PhaseCtx& c) {
     Range range_("satba:solve");
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(p->device));
     double* S = p->payload();
     double* rhs = S + (size_t)p->n_c * p->n_c;
     if (p->n_c <= CH_ONE_LAUNCH) {
         hipLaunchKernelGGL(k_solve_small, dim3(1), dim3(256), 0, p->stream, p->n_c, p->d_scale_inv, S, rhs, p->d_dch, p->d_dc, p->d_fail, 1 + CH_MAX_STEPS,
-                           (int)p->hdr, p->d_xb, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, p->gate);
+                           (int)p->hdr, p->d_xb, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, c.gate);
         HIP_TRY(hipGetLastError());
-        TRY(launch_backsub_kernel(p));
+        TRY(launch_backsub_kernel(p, c.gate));
         p->have_step = true;
         return 0;
     }
     if (p->s_scaled) p->s_scaled = false;  // k_schur_finish has scaled the system and cleared the solver's status words
     else hipLaunchKernelGGL(k_scale_system, dim3(grid_for((long long)p->n_c * p->n_c, 256, 2048)), dim3(256), 0, p->stream, p->n_c,
-                            p->d_scale_inv, S, rhs, p->d_dch, p->d_fail, 1 + CH_MAX_STEPS, p->gate, 0, p->n_c);
+                            p->d_scale_inv, S, rhs, p->d_dch, p->d_fail, 1 + CH_MAX_STEPS, c.gate, 0, p->n_c);
     HIP_TRY(hipGetLastError());
     bool unscaled = false;
-    TRY(dense_solve(p, S, p->d_dch, true, &unscaled));  // the not-SPD flag and the step flags were cleared by the scaling kernel
+    TRY(dense_solve(p, c.gate, S, p->d_dch, true, &unscaled));  // the not-SPD flag and the step flags were cleared by the scaling kernel
     if (!unscaled) {
         const int nu = std::max(p->n_c, (int)p->hdr);
         hipLaunchKernelGGL(k_unscale, dim3((nu + 255) / 256), dim3(256), 0, p->stream, p->n_c, p->d_scale_inv, p->d_dch, p->d_dc, (int)p->hdr,
-                           p->d_xb, p->d_fail, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, p->gate);
+                           p->d_xb, p->d_fail, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, c.gate);
         HIP_TRY(hipGetLastError());
     }
-    TRY(launch_backsub_kernel(p));
+    TRY(launch_backsub_kernel(p, c.gate));
     p->have_step = true;
     return 0;
 }
-
-int satba_subspace(satba_problem* p, double alpha, double inv_norm_g) {
-    Range range_("satba:subspace");
+int satba_solve(satba_problem* p) {
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->have_step) return fail(SATBA_E_STATE, "subspace before solve");
     HIP_TRY(hipSetDevice(p->device));
-    if (!p->gate) TRY(zero_header(p));  // (the device-resident loop reads only the slots this phase writes)
+    return solve_impl(p, PhaseCtx{});
+}
+
+static int subspace_impl(satba_problem* p, const PhaseCtx& c, double alpha, double inv_norm_g) {
+    Range range_("satba:subspace");
+    if (!p->have_step) return fail(SATBA_E_STATE, "subspace before solve");
+    if (!c.gate) TRY(zero_header(p));  // (the device-resident loop reads only the slots this phase writes)
     hipLaunchKernelGGL(k_subspace_vec, dim3(grid_for(p->n, 256, 512)), dim3(256), 0, p->stream, p->n, p->n_c, p->lead, alpha,
-                       inv_norm_g, p->d_gh, p->d_gn, p->d_q1, p->d_wv, p->red(RB_SUB), p->d_xb, p->sub_args_dev, p->gate);
+                       inv_norm_g, p->d_gh, p->d_gn, p->d_q1, p->d_wv, p->red(RB_SUB), p->d_xb, c.sub_args_dev, c.gate);
     HIP_TRY(hipGetLastError());
     return 0;
 }
+int satba_subspace(satba_problem* p, double alpha, double inv_norm_g) {
+    if (!p) return fail(SATBA_E_ARG, "null handle");
+    HIP_TRY(hipSetDevice(p->device));
+    return subspace_impl(p, PhaseCtx{}, alpha, inv_norm_g);
+}
 
-int satba_subspace_products(satba_problem* p) {
+static int subspace_products_impl(satba_problem* p, const PhaseCtx& c) {
     Range range_("satba:subspace_products");
-    if (!p) return fail(SATBA_E_ARG, "null handle");
     if (!p->have_step) return fail(SATBA_E_STATE, "subspace_products before solve");
+    if (!c.gate) TRY(zero_header(p));
+    return launch_jvp(p, c.gate, 2, p->d_q1, p->d_wv, p->d_xb + 3);
+}
+int satba_subspace_products(satba_problem* p) {
+    if (!p) return fail(SATBA_E_ARG, "null handle");
     HIP_TRY(hipSetDevice(p->device));
-    if (!p->gate) TRY(zero_header(p));
-    TRY(launch_jvp(p, 2, p->d_q1, p->d_wv, p->d_xb + 3));
-    return 0;
+    return subspace_products_impl(p, PhaseCtx{});
 }
 
-static int trial_impl(satba_problem* p, double c0, double c1, const double* v0, const double* v1) {
-    TRY(launch_trial(p, c0, c1, v0, v1));  // k_trial_cams clears the header
-    return 0;
+// the trial point x + c0 v0 + c1 v1: gn, along (g_h, gn_h) (satba_trial_gn), else along the subspace vectors (q1, w)
+static int trial_impl(satba_problem* p, const PhaseCtx& c, bool gn, double c0, double c1) {
+    Range range_("satba:trial");
+    if (!p->have_step) return fail(SATBA_E_STATE, "trial before solve");
+    return launch_trial(p, c, c0, c1, gn ? p->d_gh : p->d_q1, gn ? p->d_gn : p->d_wv);  // k_trial_cams clears the header
 }
-
 int satba_trial(satba_problem* p, double p0, double p1) {
-    Range range_("satba:trial");
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->have_step) return fail(SATBA_E_STATE, "trial before solve");
     HIP_TRY(hipSetDevice(p->device));
-    return trial_impl(p, p0, p1, p->d_q1, p->d_wv);
+    return trial_impl(p, PhaseCtx{}, false, p0, p1);
 }
-
 int satba_trial_gn(satba_problem* p, double ca, double cb) {
-    Range range_("satba:trial");
     if (!p) return fail(SATBA_E_ARG, "null handle");
-    if (!p->have_step) return fail(SATBA_E_STATE, "trial before solve");
     HIP_TRY(hipSetDevice(p->device));
-    return trial_impl(p, ca, cb, p->d_gh, p->d_gn);
+    return trial_impl(p, PhaseCtx{}, true, ca, cb);
 }
 
 int satba_accept(satba_problem* p) {
@@ -1899,12 +1912,7 @@ int satba_read_header(satba_problem* p, double* host_hdr) {
 // The loop of satba/trf.py (scipy's trf_no_bounds with an exact damped step) below the ABI: single rank only -- with several
 // ranks the exchange buffer has to be all-reduced between the phases, which is the caller's side of the contract.
 // single-rank loops: linearize with the point part of the prepare phase fused into k_linearize (ObsArgs::prep_*)
-static int linearize_fused(satba_problem* p, bool first) {
-    p->fuse_prep = first ? 1 : 0;
-    const int rc = satba_linearize(p);
-    p->fuse_prep = -1;
-    return rc;
-}
+static PhaseCtx fused_prep_ctx(bool first) { PhaseCtx c; c.fuse_prep = first ? 1 : 0; return c; }
 
 // quadratic model of the cost on the orthonormal basis of span{g_h, gn_h} (satba/trf.py:subspace_model): B (2 x 2, entries Ba Bb Bc),
 // gradient (gS0, gS1), and what maps a step (p0, p1) on that basis back to coefficients of (g_h, gn_h).  h: header of the solve
@@ -1923,7 +1931,7 @@ static int lm_subspace_model(satba_problem* p, const double* h, double* tmp, dou
         b12 = (m12 - alpha * m11) / sa;
         b22 = m22 - 2.0 * alpha * m12 + alpha * alpha * m11;
     } else {
-        TRY(satba_subspace(p, alpha, 1.0 / sa));
+        TRY(subspace_impl(p, PhaseCtx{}, alpha, 1.0 / sa));
         TRY(satba_read_header(p, tmp));
         ww = tmp[WW]; ghw = tmp[GHW];
         if (!(ww > 1e-24 * gc && ww > 0)) {
@@ -1931,7 +1939,7 @@ static int lm_subspace_model(satba_problem* p, const double* h, double* tmp, dou
             b11 = jg_sq / ga; b12 = 0.0; b22 = 1.0; nw = 1.0; ww = 1.0; ghw = 0.0;
         } else {
             nw = std::sqrt(ww);
-            TRY(satba_subspace_products(p));
+            TRY(subspace_products_impl(p, PhaseCtx{}));
             TRY(satba_read_header(p, tmp));
             b11 = tmp[B11]; b12 = tmp[B12]; b22 = tmp[B22];
         }
@@ -1951,12 +1959,13 @@ int satba_lm_step(satba_problem* p, int32_t first, double Delta, double lam_floo
     if (!p || !out) return fail(SATBA_E_ARG, "null argument");
     if (p->world != 1) return fail(SATBA_E_ARG, "satba_lm_step drives a single-rank handle (world = %d): use the phase entry points", p->world);
     enum { COST_NEW = 1, K_COST = SATBA_HDR_KEEP, K_GINF, K_GH_SQ, K_JG_SQ, K_XS_SQ, K_LAM, K_DELTA };
+    HIP_TRY(hipSetDevice(p->device));
     std::vector<double> hbuf((size_t)p->hdr), tbuf((size_t)p->hdr);
     double* h = hbuf.data();
     for (;;) {
-        TRY(linearize_fused(p, first != 0));
-        TRY(satba_prepare(p, first ? 1 : 0));
-        TRY(front_schur_solve(p, true, 0.0, first ? -1.0 : Delta, lam_floor));
+        TRY(linearize_impl(p, fused_prep_ctx(first != 0)));
+        TRY(prepare_impl(p, PhaseCtx{}, first ? 1 : 0));
+        TRY(front_schur_solve(p, PhaseCtx{}, true, 0.0, first ? -1.0 : Delta, lam_floor));
         TRY(satba_read_header(p, h));
         if (h[SATBA_HDR_FX_BAD] == 0.0 || !p->cam_sums_lds) break;
         TRY(satba_camera_sums_fallback(p));  // a term left the fixed-point range: camera-major sums from here on
@@ -1965,7 +1974,7 @@ int satba_lm_step(satba_problem* p, int32_t first, double Delta, double lam_floo
     for (int attempt = 0; attempt < 10; ++attempt) {  // a failed factorisation is repeated with more damping, as satba_solve_lm does
         if (h[4] == 0 && std::isfinite(h[3])) break;
         if (!beside_timed_out(p, h)) reg = std::fmax(reg, 1e-16) * 100.0;
-        TRY(front_schur_solve(p, false, reg, 0.0, 0.0));
+        TRY(front_schur_solve(p, PhaseCtx{}, false, reg, 0.0, 0.0));
         TRY(satba_read_header(p, h));
     }
     const double cost = h[K_COST], jg_sq = h[K_JG_SQ];
@@ -1976,7 +1985,7 @@ int satba_lm_step(satba_problem* p, int32_t first, double Delta, double lam_floo
     const bool newton = satba_lm::solve_trust_region_2d(md.Ba, md.Bb, md.Bc, md.gS0, md.gS1, Delta, p0, p1);
     const double predicted = -(0.5 * (p0 * (md.Ba * p0 + md.Bb * p1) + p1 * (md.Bb * p0 + md.Bc * p1)) + md.gS0 * p0 + md.gS1 * p1);
     const double ca = md.one_dim ? p0 / md.sa : p0 / md.sa - p1 * md.alpha / md.nw, cb = md.one_dim ? 0.0 : p1 / md.nw;
-    TRY(satba_trial_gn(p, ca, cb));
+    TRY(trial_impl(p, PhaseCtx{}, true, ca, cb));
     TRY(satba_read_header(p, tbuf.data()));
     const double cost_new = tbuf[COST_NEW];
     const double step_h_norm = satba_lm::norm2(p0, p1);
@@ -2011,25 +2020,23 @@ static int lm_reset(satba_problem* p, const satba_lm_opts* o, bool never_stop, b
     return 0;
 }
 
-// one tick (satba_lmdev.h): every launch is gated by the loop's state, nothing waits for the device
-struct LmArgsScope {  // while a pattern is being queued the launchers read the loop's scalars from its state in device memory
-    satba_problem* p;
-    explicit LmArgsScope(satba_problem* q) : p(q) {
-        LmDev* st = p->d_lm;
-        p->Delta_dev = &st->Delta; p->first_dev = &st->first; p->lam_force_dev = &st->lam_force; p->coef_dev = st->coef; p->sub_args_dev = st->sub_args;
-    }
-    ~LmArgsScope() { p->gate = nullptr; p->Delta_dev = nullptr; p->first_dev = nullptr; p->coef_dev = nullptr; p->lam_force_dev = nullptr; p->sub_args_dev = nullptr; }
-};
-
-static int lm_launch_tail(satba_problem* p) {  // trial evaluation, decision, accepted point (or the kept one) into place
+// one tick (satba_lmdev.h): every launch is gated by the loop's state, nothing waits for the device.  lm_ctx: the context of one part
+// of the pattern -- switched by `gate`, the launchers read the loop's scalars from its state in device memory
+static PhaseCtx lm_ctx(const satba_problem* p, const int* gate) {
     LmDev* st = p->d_lm;
-    p->gate = &st->run_trial;
+    PhaseCtx c;
+    c.gate = gate; c.Delta_dev = &st->Delta; c.first_dev = &st->first; c.lam_force_dev = &st->lam_force; c.coef_dev = st->coef; c.sub_args_dev = st->sub_args;
+    return c;
+}
+
+// trial evaluation, decision, accepted point (or the kept one) into place; decide1a: k_lm_decide1a rides in the trial's first launch
+static int lm_launch_tail(satba_problem* p, bool decide1a) {
+    LmDev* st = p->d_lm;
     // the second decision rides in the trial's residual kernel (TrialArgs::lm_st; SATBA_DECIDE2_FUSED=0: the launch of its own)
     static const bool fuse2 = !(getenv("SATBA_DECIDE2_FUSED") && atoi(getenv("SATBA_DECIDE2_FUSED")) == 0);
-    p->decide2_fused = fuse2;
-    const int rc_trial = satba_trial_gn(p, 0.0, 0.0);
-    p->decide2_fused = false;
-    TRY(rc_trial);
+    PhaseCtx c = lm_ctx(p, &st->run_trial);
+    c.decide1a_in_trial = decide1a; c.decide2_in_trial = fuse2;
+    TRY(trial_impl(p, c, true, 0.0, 0.0));
     if (!fuse2) hipLaunchKernelGGL(k_lm_decide2, dim3(1), dim3(1), 0, p->stream, st, p->d_xb, p->h_lm_dev);
     const double* x0 = p->d_x0;
     // the scales of the next tick's fixed-point camera sums ride in this launch (k_lm_accept_scales; SATBA_SCALES_IN_ACCEPT=0: k_lin_scales in every tick)
@@ -2054,32 +2061,23 @@ static int lm_launch_tail(satba_problem* p) {  // trial evaluation, decision, ac
 
 static int lm_launch_tick(satba_problem* p, double lam_floor) {
     LmDev* st = p->d_lm;
-    LmArgsScope scope(p);
-    p->gate = &st->run_lin;
-    p->fuse_prep = 0;  // (`first` comes from the loop's state)
-    p->skip_lin_scales = p->scales_by_tail && p->cam_sums_lds;
-    const int rc_lin = satba_linearize(p);
-    p->skip_lin_scales = false;
-    p->fuse_prep = -1;
-    TRY(rc_lin);
-    TRY(satba_prepare(p, 0));
-    p->gate = &st->run_solve;
-    TRY(front_schur_solve(p, true, 0.0, -1.0, lam_floor));
-    p->decide_fused = true;  // k_lm_decide1a rides in the trial's first launch (launch_trial)
-    return lm_launch_tail(p);
+    PhaseCtx lin = lm_ctx(p, &st->run_lin);
+    lin.fuse_prep = 0;  // (`first` comes from the loop's state)
+    lin.skip_lin_scales = p->scales_by_tail && p->cam_sums_lds;
+    TRY(linearize_impl(p, lin));
+    TRY(prepare_impl(p, lm_ctx(p, &st->run_lin), 0));
+    TRY(front_schur_solve(p, lm_ctx(p, &st->run_solve), true, 0.0, -1.0, lam_floor));
+    return lm_launch_tail(p, true);
 }
 
 // the pattern of the degenerate case (g_h and gn_h parallel to 1e-6): explicit subspace vectors and products, then the tail
 static int lm_launch_sub_pattern(satba_problem* p) {
     LmDev* st = p->d_lm;
-    LmArgsScope scope(p);
-    p->gate = &st->run_sub;
-    TRY(satba_subspace(p, 0.0, 0.0));
+    TRY(subspace_impl(p, lm_ctx(p, &st->run_sub), 0.0, 0.0));
     hipLaunchKernelGGL(k_lm_decide1b, dim3(1), dim3(1), 0, p->stream, st, p->d_xb);
-    p->gate = &st->run_prod;
-    TRY(satba_subspace_products(p));
+    TRY(subspace_products_impl(p, lm_ctx(p, &st->run_prod)));
     hipLaunchKernelGGL(k_lm_decide1c, dim3(1), dim3(1), 0, p->stream, st, p->d_xb);
-    return lm_launch_tail(p);
+    return lm_launch_tail(p, false);
 }
 
 // one tick (direct launches: a captured hipGraph of the pattern was measured in round 3 -- 2 - 9 us between its nodes where back-to-back
@@ -2207,29 +2205,27 @@ int satba_lm_part(satba_problem* p, int32_t part, double lam_floor) {
     if (!p || part < 0 || part > 12) return fail(SATBA_E_ARG, "bad argument");
     HIP_TRY(hipSetDevice(p->device));
     LmDev* st = p->d_lm;
-    LmArgsScope scope(p);
     switch (part) {
-        case 0: p->gate = &st->run_lin; return satba_linearize(p);
-        case 1: p->gate = &st->run_lin; return satba_prepare(p, 0);
-        case 2: p->gate = &st->run_solve; return satba_schur_auto(p, -1.0, lam_floor);
-        case 3: p->gate = &st->run_solve; return satba_solve(p);
-        case 4:
-            p->decide_fused = true;  // k_lm_decide1a rides in the trial's first launch (launch_trial)
-            p->gate = &st->run_trial;
-            return satba_trial_gn(p, 0.0, 0.0);
+        case 0: return linearize_impl(p, lm_ctx(p, &st->run_lin));
+        case 1: return prepare_impl(p, lm_ctx(p, &st->run_lin), 0);
+        case 2: return schur_impl(p, lm_ctx(p, &st->run_solve), FrontCtx{}, 0.0, true, -1.0, lam_floor);
+        case 3: return solve_impl(p, lm_ctx(p, &st->run_solve));
+        case 4: {
+            PhaseCtx c = lm_ctx(p, &st->run_trial);
+            c.decide1a_in_trial = true;  // k_lm_decide1a rides in the trial's first launch (launch_trial)
+            return trial_impl(p, c, true, 0.0, 0.0);
+        }
         // the solve phase with the all-reduce of S in messages (trf.drive_device_loop): 10 begin, 11 message lam_floor has arrived, 12 end
-        case 10: p->gate = &st->run_solve; return satba_solve_messages_begin(p, p->msg_packed, lam_floor != 0.0 ? 1 : 0);
-        case 11: p->gate = &st->run_solve; return satba_solve_messages_arrived(p, p->msg_packed, (int)lam_floor);
-        case 12: p->gate = &st->run_solve; return satba_solve_messages_end(p);
-        case 6: p->gate = &st->run_sub; return satba_subspace(p, 0.0, 0.0);
+        case 10: return solve_messages_begin_impl(p, &st->run_solve, p->msg_packed, lam_floor != 0.0 ? 1 : 0);
+        case 11: return solve_messages_arrived_impl(p, &st->run_solve, p->msg_packed, (int)lam_floor);
+        case 12: return solve_messages_end_impl(p, &st->run_solve);
+        case 6: return subspace_impl(p, lm_ctx(p, &st->run_sub), 0.0, 0.0);
         case 7:
             hipLaunchKernelGGL(k_lm_decide1b, dim3(1), dim3(1), 0, p->stream, st, p->d_xb);
-            p->gate = &st->run_prod;
-            return satba_subspace_products(p);
+            return subspace_products_impl(p, lm_ctx(p, &st->run_prod));
         case 8:
             hipLaunchKernelGGL(k_lm_decide1c, dim3(1), dim3(1), 0, p->stream, st, p->d_xb);
-            p->gate = &st->run_trial;
-            return satba_trial_gn(p, 0.0, 0.0);
+            return trial_impl(p, lm_ctx(p, &st->run_trial), true, 0.0, 0.0);
         default: break;  // 5, 9: decision, accepted point into place
     }
     hipLaunchKernelGGL(k_lm_decide2, dim3(1), dim3(1), 0, p->stream, st, p->d_xb, p->h_lm_dev);
@@ -2287,9 +2283,9 @@ static int lm_host_loop(satba_problem* p, const satba_lm_opts* o, satba_lm_stats
     double* h = hbuf.data();
     auto front = [&](double Delta, bool first) -> int {
         for (;;) {
-            TRY(linearize_fused(p, first));
-            TRY(satba_prepare(p, first ? 1 : 0));
-            TRY(front_schur_solve(p, true, 0.0, first ? -1.0 : Delta, 0.0));
+            TRY(linearize_impl(p, fused_prep_ctx(first)));
+            TRY(prepare_impl(p, PhaseCtx{}, first ? 1 : 0));
+            TRY(front_schur_solve(p, PhaseCtx{}, true, 0.0, first ? -1.0 : Delta, 0.0));
             TRY(satba_read_header(p, h));
             if (h[SATBA_HDR_FX_BAD] == 0.0 || !p->cam_sums_lds) return 0;
             TRY(satba_camera_sums_fallback(p));  // a term left the fixed-point range: camera-major sums from here on
@@ -2338,7 +2334,7 @@ static int lm_host_loop(satba_problem* p, const satba_lm_opts* o, satba_lm_stats
         for (; attempt < 10; ++attempt) {  // a Cholesky needs a floor where LSMR copes with a numerically singular system
             if (h[CHOL_FAIL] == 0 && std::isfinite(h[GRAM_C])) break;
             if (!beside_timed_out(p, h)) reg = std::fmax(reg, 1e-16) * 100.0;
-            TRY(front_schur_solve(p, false, reg, 0.0, 0.0));
+            TRY(front_schur_solve(p, PhaseCtx{}, false, reg, 0.0, 0.0));
             TRY(satba_read_header(p, h));
         }
         if (attempt == 10) return fail(SATBA_E_STATE, "reduced camera system could not be factorised");
@@ -2353,7 +2349,7 @@ static int lm_host_loop(satba_problem* p, const satba_lm_opts* o, satba_lm_stats
             satba_lm::solve_trust_region_2d(Ba, Bb, Bc, gS0, gS1, Delta, p0, p1);
             const double predicted = -(0.5 * (p0 * (Ba * p0 + Bb * p1) + p1 * (Bb * p0 + Bc * p1)) + gS0 * p0 + gS1 * p1);
             const double ca = one_dim ? p0 / sa : p0 / sa - p1 * alpha / nw, cb = one_dim ? 0.0 : p1 / nw;
-            TRY(satba_trial_gn(p, ca, cb));
+            TRY(trial_impl(p, PhaseCtx{}, true, ca, cb));
             TRY(satba_read_header(p, tbuf.data()));
             const double cost_new = tbuf[COST_NEW];
             ++nfev;
@@ -2446,7 +2442,7 @@ int satba_get_blocks(satba_problem* p, double* U, double* gc, double* V, double*
                 TRY(launch_residual(p, false, p->d_f, p->d_scal));
                 p->f_valid = true;
             }
-            TRY(launch_cam_sums(p, dU, dg));
+            TRY(launch_cam_sums(p, nullptr, dU, dg));
             HIP_TRY(hipStreamSynchronize(p->stream));
             HIP_TRY(hipMemcpy(U, dU, sizeof(double) * nU, hipMemcpyDeviceToHost));
             return 0;
@@ -2614,14 +2610,14 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
     auto once = [&]() -> int {
         switch (phase) {
             case 0: return launch_residual(p, false, p->d_f, p->d_scal);
-            case 1: return launch_linearize_kernel(p);
-            case 2: return launch_schur_kernel(p);
+            case 1: return launch_linearize_kernel(p, PhaseCtx{});
+            case 2: return launch_schur_kernel(p, nullptr, FrontCtx{});
             case 3: {
                 // factorising an already factorised matrix is meaningless numerically but identical in work
-                return dense_solve(p, p->payload(), p->d_dch);
+                return dense_solve(p, nullptr, p->payload(), p->d_dch);
             }
-            case 4: return launch_backsub_kernel(p);
-            default: return launch_jvp(p, 1, p->d_q1, p->d_q1, p->d_scal, true);  // the pass of the prepare phase
+            case 4: return launch_backsub_kernel(p, nullptr);
+            default: return launch_jvp(p, nullptr, 1, p->d_q1, p->d_q1, p->d_scal, true);  // the pass of the prepare phase
         }
     };
     rc = once();  // warm-up

@@ -589,3 +589,33 @@ def test_bench_line_two_ranks(gpu, tmp_path, driver):
     assert d["accepted_steps"] >= 4 and d["config"]["obs_per_rank0"] < 29981  # a shard, not the whole scene
     # the outputs are the whole point: both ranks' points gathered
     assert np.load(tmp_path / "x_points.npy").shape == (5000, 3) and np.load(tmp_path / "cost.npy")[0] == d["final_cost"]
+
+
+@pytest.mark.parametrize("refused", ["lm_part", "lm_run"])
+def test_refused_device_loop_call_leaves_nothing_on_the_handle(gpu, refused):
+    """A call of the device-resident loop that is refused must not change what the next host-driven solve launches: what a caller
+    wants of the next phase travels as an argument of the launchers, not on the handle.  lm_part: part 4 of the several-rank loop
+    (k_lm_decide1a riding in the trial's first launch) on a fresh handle -- trial before solve; lm_run: the one-rank loop with cycles
+    but no kept point (the only refusal of that loop the ABI reaches without a solve; its ticks linearise first and refuse nothing).
+    The four Python-driven iterations behind it (satba_trial among their phases) equal those of a handle that saw no refused call."""
+    import bench
+    from satba.engine_hip import SatbaError
+
+    _, make_p, _, _ = cases.solve_case("affine_small_R")
+    runs = []
+    for refuse in (True, False):
+        eng = HipEngine(make_p())
+        eng.configure("linear", 1.0)
+        eng.lm_begin()
+        if refuse:
+            with pytest.raises(SatbaError):
+                eng.lm_part(4) if refused == "lm_part" else eng.lm_run(4, cycle_len=2)
+        st = {"first": True, "accepted": 0, "fail": 0, "cost": None}
+        trace = []
+        for _ in range(4):
+            bench.lm_step(eng, trf.SingleComm(), st, trf)
+            trace.append((st["cost"], st["Delta"], st["accepted"]))
+        runs.append((eng.get_x(), trace))
+        eng.close()
+    assert np.array_equal(runs[0][0], runs[1][0])
+    assert runs[0][1] == runs[1][1], (runs[0][1], runs[1][1])
