@@ -62,6 +62,51 @@ enum {
 #define SATBA_HDR_KEEP 8
 #define SATBA_KEEP_LEN 8
 #define SATBA_HDR_FX_BAD 15
+/* The fixed slots, per phase: every phase zeroes the header and then gives the low slots its own meaning (the same table, with the
+ * same values, is satba/trf.py's; tests/test_host_logic.py holds the two together). */
+/* left by satba_linearize (rank r also leaves |g_p|_inf of its shard in slot SATBA_HDR_FIXED + r): */
+#define SATBA_HDR_COST 0
+#define SATBA_HDR_FX 5      /* a term of the fixed-point camera sums exceeded its bound (summed over ranks) */
+#define SATBA_HDR_PREP_GH 6 /* point sums of |g_h|^2, |x_h|^2 when the linearisation did the point part of the prepare phase */
+#define SATBA_HDR_PREP_XS 7
+/* left by satba_prepare: |g_h|^2, |J_h g_h|^2, |x_h|^2, lead * |g_c|_inf */
+#define SATBA_HDR_GH_SQ 1
+#define SATBA_HDR_JG_SQ 2
+#define SATBA_HDR_XS_SQ 3
+#define SATBA_HDR_GC_INF 4
+/* left by satba_solve and satba_solve_messages_end: Gram matrix of (g_h, gn_h), status word of the factorisation (written by rank 0
+ * alone: headers are summed over the ranks), and the kept scalars in slots SATBA_HDR_KEEP + SATBA_KEEP_* (the last of them is
+ * SATBA_HDR_FX_BAD) */
+#define SATBA_HDR_GRAM_A 1
+#define SATBA_HDR_GRAM_B 2
+#define SATBA_HDR_GRAM_C 3
+#define SATBA_HDR_CHOL_FAIL 4
+#define SATBA_KEEP_COST 0
+#define SATBA_KEEP_GINF 1
+#define SATBA_KEEP_GH_SQ 2
+#define SATBA_KEEP_JG_SQ 3
+#define SATBA_KEEP_XS_SQ 4
+#define SATBA_KEEP_LAM 5
+#define SATBA_KEEP_DELTA 6
+#define SATBA_KEEP_FX_BAD 7
+/* bits of the status word in SATBA_HDR_CHOL_FAIL (0: factorised): the system is not positive definite; a wait timed out; that wait
+ * was one BETWEEN the factorisation and the kernel producing its input beside it on another stream -- the two did not run at the same
+ * time, the front is repeated one kernel after the other with the same damping (one rank: the word is >= SATBA_CHOL_BESIDE_WAIT) */
+#define SATBA_CHOL_NOT_SPD 1
+#define SATBA_CHOL_TIMEOUT 2
+#define SATBA_CHOL_BESIDE_WAIT 4
+/* left by satba_subspace: w.w, w.q1, g_h.w */
+#define SATBA_HDR_WW 1
+#define SATBA_HDR_WQ1 2
+#define SATBA_HDR_GHW 6
+/* left by satba_subspace_products: |J_h q1|^2, (J_h q1).(J_h w), |J_h w|^2 */
+#define SATBA_HDR_B11 3
+#define SATBA_HDR_B12 4
+#define SATBA_HDR_B22 5
+/* left by satba_trial and satba_trial_gn: cost at x_new, |step|^2, |x|^2 */
+#define SATBA_HDR_COST_NEW 1
+#define SATBA_HDR_STEP_SQ 2
+#define SATBA_HDR_X_SQ 3
 
 typedef struct satba_problem satba_problem;
 
@@ -158,7 +203,7 @@ int satba_get_x(satba_problem *p, double *host_x);
 int satba_residuals(satba_problem *p, double *host_r, double *host_cost);
 
 /* ---- phases of one trust-region iteration (satba/trf.py; scipy:optimize/_lsq/trf.py:450-551).
- * Each phase zeroes the exchange header, then writes the slots documented in satba/trf.py.               */
+ * Each phase zeroes the exchange header, then writes its slots (SATBA_HDR_* above).                        */
 
 /* residuals + analytic Jacobian -> normal-equation blocks at x.  Replaces scipy's finite-difference
  * Jacobian (scipy:optimize/_numdiff.py:628-705), compute_grad (common.py:590-595) and the robust
@@ -183,7 +228,7 @@ int satba_solve(satba_problem *p);
  * The quadratic model on that basis (trf.py:483-485) follows on the host from the normal equations,
  * J_h^T J_h gn_h = g_h - reg gn_h, without another pass over the observations (satba/trf.py);
  * satba_subspace_products computes the three products |J_h q1|^2, (J_h q1).(J_h w), |J_h w|^2 explicitly
- * (header slots 3..5) for the ill-conditioned case and for the tests.                                      */
+ * (header slots SATBA_HDR_B11 .. _B22) for the ill-conditioned case and for the tests.                                      */
 int satba_subspace(satba_problem *p, double alpha, double inv_norm_g);
 int satba_subspace_products(satba_problem *p);
 /* x_new = x + scale * (p0 q1 + p1 w); cost at x_new (trf.py:497-512).                                     */

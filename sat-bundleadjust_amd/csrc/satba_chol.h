@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/satba.h"
+
 // gate of the device-resident LM loop (satba_kernels.h): a kernel returns at once when its gate word is 0; null: no gate
 #ifndef SATBA_GATE
 #define SATBA_GATE(g) do { if ((g) != nullptr && *(g) == 0) return; } while (0)
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(1024) void k_trsv_back(const double* __restrict__ L
 // flag: one int per superblock, zero on entry.  All workgroups are resident (at most 8 of them).
 constexpr int CH_SB = 128;
 // What follows the substitution in the solve phase (k_unscale), done by the last workgroup of k_trsv_back_mw when dc is set: the step in
-// unscaled variables dc = z / scale_inv and the header of the phase (zero; slot 4 = lead x status word; the kept scalars) -- one
+// unscaled variables dc = z / scale_inv and the header of the phase (zero; SATBA_HDR_CHOL_FAIL = lead x status word; the kept scalars) -- one
 // launch less per iteration when the kernels run one after the other (4.8 us of 322 at 50 cameras).
 struct TrsvTail {
     double* dc = nullptr;
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(512) void k_trsv_back_mw(const double* __restrict__
         for (int i = tid; i < n; i += 512) tail.dc[i] = __hip_atomic_load(b + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / tail.scale_inv[i];
         for (int i = tid; i < tail.hdr_len; i += 512) {
             double v = 0.0;
-            if (i == 4) v = tail.lead * (double)*tail.fail;
+            if (i == SATBA_HDR_CHOL_FAIL) v = tail.lead * (double)*tail.fail;
             if (i >= tail.keep_at && i < tail.keep_at + tail.keep_len) v = tail.lead * tail.keep[i - tail.keep_at];
             tail.hdr[i] = v;
         }
@@ -268,7 +270,7 @@ inline void cholesky_tiles(double* A, int n, double* b, int* fail, hipStream_t s
 }
 
 // Factorise A (n x n, column-major lower, in place) and solve A z = b in place.  *fail != 0 if A was not SPD (or a wait inside the
-// tile kernel timed out: bit 1).  flags: CH_MAX_STEPS ints of scratch directly behind *fail (flags == fail + 1); both are cleared here
+// tile kernel timed out: SATBA_CHOL_TIMEOUT).  flags: CH_MAX_STEPS ints of scratch directly behind *fail (flags == fail + 1); both are cleared here
 // unless `cleared` (satba_solve does it in its scaling kernel).  dinv: (n / 32 rounded up) x 1024 doubles of scratch.
 // ts (tools): C3_TS time stamps per step of the tile kernel (a build with -DC3_STAMPS).
 // tail (or null): what k_unscale does, by the backward substitution's last workgroup where that kernel runs (returns true), else left to the caller

@@ -22,7 +22,7 @@
 // (guide: Guideline 16, form R1 with 8-byte agent-scope accesses on both sides); flags hold 4 x epoch + stage, the epoch counts
 // launches, so nothing has to be cleared between launches.  Tasks are handed out by a ticket counter in column-major tile order:
 // a workgroup only ever waits for tiles with smaller tickets (or for the chain, ticket 0), so the kernel makes progress whatever
-// part of the grid is resident.  Every spin is bounded (fail |= 2 after ~1 s).
+// part of the grid is resident.  Every spin is bounded (fail |= SATBA_CHOL_TIMEOUT after ~1 s).
 #pragma once
 #include <type_traits>
 
@@ -41,7 +41,7 @@ struct C3Args {
     double* A;        // n x n, column-major, lower triangle valid; L in place on return (and L^T in the strict upper triangle if mirror)
     int n;
     double* b;        // right-hand side; y = L^-1 b on return
-    int* fail;        // |= 1 not positive definite, |= 2 a wait timed out, |= 4 (with 2) it was a wait for the kernel that produces the matrix (c3_wait_arrive)
+    int* fail;        // status word, |= SATBA_CHOL_NOT_SPD, SATBA_CHOL_TIMEOUT, SATBA_CHOL_BESIDE_WAIT (with TIMEOUT: set by c3_wait_arrive) -- include/satba.h
     int* flags;       // T x T tile flags (never cleared: epochs)
     int epoch;        // > 0, larger at every launch
     double* Linv;     // T x 64 x 64: column-major inverses of the diagonal blocks
@@ -58,7 +58,7 @@ struct C3Args {
     // agent-scope loads.
     int* arrive = nullptr;
     int arr_M = 0, np = 1, arr_epoch = 0, nap = 1;  // nap: length of a pause between two looks at the counters, in units of ~0.5 us
-    // how long a tile waits for its producers before it gives up (fail |= 2: the two kernels are not running at the same time), in
+    // how long a tile waits for its producers before it gives up (fail |= SATBA_CHOL_TIMEOUT: the two kernels are not running at the same time), in
     // ticks of the 100 MHz wall clock.  Round 4 counted spins (~0.3 - 1 s); the caller now passes a few milliseconds plus a
     // multiple of the pair kernel's expected duration, so that a fall-back to the sequential front costs ~10 ms
     long long arr_timeout = C3_ARRIVE_TIMEOUT;
@@ -177,8 +177,8 @@ __device__ __forceinline__ bool c3_wait(const int* f, int want, int* fail) {
     while ((int)(c3_ld_flag(f) - want) < 0) {
         __builtin_amdgcn_s_sleep(1);
         if ((++spins & 1023) == 0) {
-            if (spins > c3_poll_limit(0)) { c3_or_fail(fail, 2); return false; }
-            if (c3_ld_flag(fail) & 2) return false;
+            if (spins > c3_poll_limit(0)) { c3_or_fail(fail, SATBA_CHOL_TIMEOUT); return false; }
+            if (c3_ld_flag(fail) & SATBA_CHOL_TIMEOUT) return false;
         }
     }
     return true;
@@ -194,8 +194,8 @@ __device__ __forceinline__ bool c3_wait_lds(const int* f, int want, int* fail, b
     while (c3_lds_get(f) < want) {
         __builtin_amdgcn_s_sleep(1);
         if ((++spins & 4095) == 0) {
-            if (spins > (kernel_limit ? c3_poll_limit(1) : 4 * C3_SPIN_LIMIT)) { c3_or_fail(fail, 2); return false; }
-            if (c3_ld_flag(fail) & 2) return false;
+            if (spins > (kernel_limit ? c3_poll_limit(1) : 4 * C3_SPIN_LIMIT)) { c3_or_fail(fail, SATBA_CHOL_TIMEOUT); return false; }
+            if (c3_ld_flag(fail) & SATBA_CHOL_TIMEOUT) return false;
         }
     }
     asm volatile("" ::: "memory");
@@ -218,8 +218,8 @@ __device__ __forceinline__ bool c3_wait_arrive(const C3Arrive& r, int col_lo, in
         if (__all(ok)) return true;
         for (int t = 0; t < r.nap; ++t) __builtin_amdgcn_s_sleep(20);
         if ((++spins & 31) == 0) {
-            if (wall_clock64() - t0 > r.timeout) { if (lane == 0) c3_or_fail(fail, 2 | 4); return false; }  // bit 2: the wait was for the PRODUCING kernel
-            if (c3_ld_flag(fail) & 2) return false;
+            if (wall_clock64() - t0 > r.timeout) { if (lane == 0) c3_or_fail(fail, SATBA_CHOL_TIMEOUT | SATBA_CHOL_BESIDE_WAIT); return false; }  // the wait was for the PRODUCING kernel
+            if (c3_ld_flag(fail) & SATBA_CHOL_TIMEOUT) return false;
         }
     }
 }
@@ -429,7 +429,7 @@ __device__ __noinline__ void c3_chain_diag(int q, double* A, int n, int T, int* 
         if (k > 0 && !c3_wait_lds(l.lf + 16 + 7, 4 * k, fail)) return;
         C3_STAMP(ts, k * C3_TS + 0, tid == 0);
         const bool bad = c3_panel(a, q, lane, l.pan, l.pinv, l.lf, step1, fail, ts ? ts + k * C3_TS + 8 : nullptr);
-        if (bad && lane == 0) c3_or_fail(fail, 1);
+        if (bad && lane == 0) c3_or_fail(fail, SATBA_CHOL_NOT_SPD);
         C3_STAMP(ts, k * C3_TS + 1, lane == 0 && q == 3);
         // ---- my 16 columns of L_kk, write-through and counted for the step's publication: the only reader in this launch is the
         // workgroup that writes L^T of the step's tiles for the back-substitution kernel (c3_mirror_task); the drain falls into the
@@ -1159,10 +1159,10 @@ __global__ __launch_bounds__(256) void k_solve_small(int n, const double* __rest
         if (c < n) { dch[c] = y; dc[c] = y / scale_inv[c]; }
     }
     const int failed = s_bad;
-    if (tid == 0 && failed) fail[0] = 1;
+    if (tid == 0 && failed) fail[0] = SATBA_CHOL_NOT_SPD;
     for (int i = tid; i < hdr_len; i += 256) {
         double v = 0.0;
-        if (i == 4) v = failed ? lead : 0.0;
+        if (i == SATBA_HDR_CHOL_FAIL) v = failed ? lead : 0.0;
         if (i >= keep_at && i < keep_at + keep_len) v = lead * keep[i - keep_at];
         hdr[i] = v;
     }

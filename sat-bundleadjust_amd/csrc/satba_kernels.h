@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/satba.h"
 #include "satba_models.h"
 
 namespace satba {
@@ -51,9 +52,6 @@ __host__ __device__ constexpr int fx_exps_len(int np) { return np + 3; }
 constexpr int RPCS = 94;
 static_assert(RPCS >= 90 && RPCS % 2 == 0 && (RPCS / 2) % 2 == 1, "RPC rows in the LDS: an odd number of 16-byte slots");
 // double -> 64-bit fixed point through one fma (k_linearize's camera sums): bits(t 2^e + 1.5 * 2^52) = FX_MAGIC_BITS + round(t 2^e)
-constexpr int SATBA_HDR_PREP_GH = 6, SATBA_HDR_PREP_XS = 7;  // linearize header: point sums of |g_h|^2, |x_h|^2 (prepare fused into k_linearize)
-constexpr int SATBA_HDR_FX = 5;  // linearize header: a term of the fixed-point camera sums exceeded its bound (summed over ranks)
-constexpr int SATBA_K_FX = 7;    // ... and its place among the kept scalars (header slot SATBA_HDR_KEEP + 7 after satba_solve)
 constexpr double FX_MAGIC = 6755399441055744.0;
 constexpr unsigned long long FX_MAGIC_BITS = 0x4338000000000000ull;
 // RPC: what a linearisation stores per observation for the passes behind it (io order): D' = diag(row scales) d(col,row)/dX', 2 x 3 =
@@ -1067,7 +1065,7 @@ __global__ void k_cam_sums_finish(int M, int NP, int n_chunks, const double* __r
 // ------------------------------------------------------------------------------------------------ prepare
 // x_scale="jac" (scipy:optimize/_lsq/common.py:598-610): scale_inv = column norms of J = sqrt(diag(J^T J)),
 // zeros -> 1 on the first evaluation, running maximum afterwards; g_h = g / scale_inv.
-// hdr[1] = |g_h|^2, hdr[3] = |x * scale_inv|^2 (camera part only if lead), hdr[4] = lead * |g_c|_inf
+// hdr[SATBA_HDR_GH_SQ] = |g_h|^2, hdr[SATBA_HDR_XS_SQ] = |x * scale_inv|^2 (camera part only if lead), hdr[SATBA_HDR_GC_INF] = lead * |g_c|_inf
 __global__ __launch_bounds__(256) void k_prepare_vec(int n, int n_c, int NP, int first, double lead,
                                                      const double* __restrict__ U, const double* __restrict__ gc_red,
                                                      const double* __restrict__ V, const double* __restrict__ x,
@@ -1077,8 +1075,8 @@ __global__ __launch_bounds__(256) void k_prepare_vec(int n, int n_c, int NP, int
     // ghs = g_h / scale_inv: the unscaled direction of g_h, input of the Jacobian-vector product that follows
     SATBA_GATE(gate);
     if (first_dev) first = *first_dev;  // device-resident loop: the first linearisation of a solve initialises the scaling
-    if (keep[SATBA_K_FX] != 0.0) return;
-    // n == n_c: the point entries were done by k_linearize (ObsArgs::prep_*); their sums wait in keep[2], keep[4] (k_prepare_stash)
+    if (keep[SATBA_KEEP_FX_BAD] != 0.0) return;
+    // n == n_c: the point entries were done by k_linearize (ObsArgs::prep_*); their sums wait in keep[SATBA_KEEP_GH_SQ], keep[SATBA_KEEP_XS_SQ] (k_prepare_stash)
     const bool fused = n == n_c;  // the camera sums of this linearisation overflowed their fixed-point range: the caller
                                           // repeats it with k_cam_sums; the running maximum of scale_inv must not see the garbage
     double s_gh = 0.0, s_xs = 0.0, m_gc = 0.0;
@@ -1109,10 +1107,10 @@ __global__ __launch_bounds__(256) void k_prepare_vec(int n, int n_c, int NP, int
         s_xs += wgt * xs * xs;
     }
     m_gc = wave_max(m_gc);
-    if ((threadIdx.x & 63) == 0 && m_gc > 0.0) atomic_max_pos(hdr + 4, lead * m_gc);
-    if (fused && blockIdx.x == 0 && threadIdx.x == 0) { s_gh += keep[2]; s_xs += keep[4]; }
+    if ((threadIdx.x & 63) == 0 && m_gc > 0.0) atomic_max_pos(hdr + SATBA_HDR_GC_INF, lead * m_gc);
+    if (fused && blockIdx.x == 0 && threadIdx.x == 0) { s_gh += keep[SATBA_KEEP_GH_SQ]; s_xs += keep[SATBA_KEEP_XS_SQ]; }
     double v[2] = {s_gh, s_xs};
-    double* const dst[2] = {hdr + 1, hdr + 3};
+    double* const dst[2] = {hdr + SATBA_HDR_GH_SQ, hdr + SATBA_HDR_XS_SQ};
     grid_sum<2>(v, dst, rb);
 }
 
@@ -1417,7 +1415,7 @@ __global__ __launch_bounds__(256) void k_scale_system(int n_c, const double* __r
 }
 
 // dc = dc_h / scale_inv (unscaled camera step for the back-substitution).  The same launch prepares the header of the
-// solve phase (nothing touches it between here and k_backsub): zero, Cholesky status in slot 4, the scalars
+// solve phase (nothing touches it between here and k_backsub): zero, Cholesky status in slot SATBA_HDR_CHOL_FAIL, the scalars
 // kept from the earlier phases of this iteration in slots SATBA_HDR_KEEP.. (rank 0 only: headers are summed over ranks)
 // done (or null): the dense solve runs on ANOTHER stream (front_schur_solve, beside the pair kernel) and posts done_epoch there when
 // dc_h is complete (k_trsv_back_mw) -- every workgroup waits for the word instead of the stream for an event (13 us from the end of
@@ -1433,22 +1431,22 @@ __global__ void k_unscale(int n_c, const double* __restrict__ scale_inv, const d
         int spins = 0;
         while ((int)(__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - done_epoch) < 0) {
             __builtin_amdgcn_s_sleep(8);
-            if (++spins > (1 << 22)) { timed_out = 2 | 4; break; }  // (~1 s: the other stream's kernels bound their own waits; bit 2: a wait between the two streams)
+            if (++spins > (1 << 22)) { timed_out = SATBA_CHOL_TIMEOUT | SATBA_CHOL_BESIDE_WAIT; break; }  // (~1 s: the other stream's kernels bound their own waits; BESIDE_WAIT: a wait between the two streams)
         }
     }
     if (i < n_c) dc[i] = (done ? __hip_atomic_load(dch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : dch[i]) / scale_inv[i];
     if (i < hdr_len) {
         double v = 0.0;
-        // (0: factorised; bit 0 not positive definite, bit 1 a wait timed out, bit 2: it was a wait of the concurrent front -- for the kernel
+        // (0: factorised; SATBA_CHOL_NOT_SPD, _TIMEOUT a wait timed out, _BESIDE_WAIT: it was a wait of the concurrent front -- for the kernel
         // on the other stream)
-        if (i == 4) v = lead * (double)((done ? __hip_atomic_load(fail_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *fail_flag) | timed_out);
+        if (i == SATBA_HDR_CHOL_FAIL) v = lead * (double)((done ? __hip_atomic_load(fail_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *fail_flag) | timed_out);
         if (i >= keep_at && i < keep_at + keep_len) v = lead * keep[i - keep_at];
         hdr[i] = v;
     }
 }
 
 // start of the prepare phase, one launch: the (already all-reduced) linearize payload U | g_c is copied out of the
-// exchange buffer, keep[0] = cost and keep[1] = max_rank |g_p|_inf are taken from its header, the header is zeroed
+// exchange buffer, keep[SATBA_KEEP_COST] = cost and keep[SATBA_KEEP_GINF] = max_rank |g_p|_inf are taken from its header, the header is zeroed
 __global__ __launch_bounds__(1024) void k_prepare_stash(int nU, int n_c, int world, int hdr_fixed, int hdr_len, double* __restrict__ xb,
                                                         double* __restrict__ U, double* __restrict__ gc, double* __restrict__ keep, const int* gate) {
     SATBA_GATE(gate);
@@ -1460,10 +1458,10 @@ __global__ __launch_bounds__(1024) void k_prepare_stash(int nU, int n_c, int wor
     if (threadIdx.x == 0) {
         double m = 0.0;
         for (int r = 0; r < world; ++r) m = fmax(m, xb[hdr_fixed + r]);
-        keep[0] = xb[0];
-        keep[1] = m;
-        keep[2] = xb[SATBA_HDR_PREP_GH]; keep[4] = xb[SATBA_HDR_PREP_XS];  // (replaced by the totals in the Schur phase)
-        keep[SATBA_K_FX] = xb[SATBA_HDR_FX];
+        keep[SATBA_KEEP_COST] = xb[SATBA_HDR_COST];
+        keep[SATBA_KEEP_GINF] = m;
+        keep[SATBA_KEEP_GH_SQ] = xb[SATBA_HDR_PREP_GH]; keep[SATBA_KEEP_XS_SQ] = xb[SATBA_HDR_PREP_XS];  // (replaced by the totals in the Schur phase)
+        keep[SATBA_KEEP_FX_BAD] = xb[SATBA_HDR_FX];
     }
     __syncthreads();
     if ((int)threadIdx.x < hdr_len) xb[threadIdx.x] = 0.0;
@@ -1489,11 +1487,11 @@ __global__ __launch_bounds__(1024) void k_prepare_cams(int nU, int n_c, int NP, 
     if (tid == 0) {
         double m = 0.0;
         for (int r = 0; r < world; ++r) m = fmax(m, xb[hdr_fixed + r]);
-        keep[0] = xb[0];
-        keep[1] = m;
+        keep[SATBA_KEEP_COST] = xb[SATBA_HDR_COST];
+        keep[SATBA_KEEP_GINF] = m;
         s_k[0] = xb[SATBA_HDR_PREP_GH]; s_k[1] = xb[SATBA_HDR_PREP_XS]; s_k[2] = xb[SATBA_HDR_FX];
-        keep[2] = s_k[0]; keep[4] = s_k[1];  // (replaced by the totals in the Schur phase)
-        keep[SATBA_K_FX] = s_k[2];
+        keep[SATBA_KEEP_GH_SQ] = s_k[0]; keep[SATBA_KEEP_XS_SQ] = s_k[1];  // (replaced by the totals in the Schur phase)
+        keep[SATBA_KEEP_FX_BAD] = s_k[2];
     }
     __syncthreads();
     if (tid < hdr_len) xb[tid] = 0.0;
@@ -1522,15 +1520,15 @@ __global__ __launch_bounds__(1024) void k_prepare_cams(int nU, int n_c, int NP, 
     if (tid == 0) {
         double a = 0.0, b = 0.0, m = 0.0;
         for (int w = 0; w < 16; ++w) { a += s_red[0][w]; b += s_red[1][w]; m = fmax(m, s_red[2][w]); }
-        xb[1] = a + s_k[0];
-        xb[3] = b + s_k[1];
-        xb[4] = lead * m;
+        xb[SATBA_HDR_GH_SQ] = a + s_k[0];
+        xb[SATBA_HDR_XS_SQ] = b + s_k[1];
+        xb[SATBA_HDR_GC_INF] = lead * m;
     }
 }
 
 // ------------------------------------------------------------------------------------------------ K5 back-substitution
 // t_p = sum_obs Jp^T (Jc dc[cam]) per point in the lane's registers, then the point part of the Gauss-Newton step in scaled
-// variables, gn_h = scale_inv_p * Vinv (g_p - t), and the Gram matrix of (g_h, gn_h): hdr[1..3] = a, b, c.  The camera part
+// variables, gn_h = scale_inv_p * Vinv (g_p - t), and the Gram matrix of (g_h, gn_h): hdr[SATBA_HDR_GRAM_A .. _C] = a, b, c.  The camera part
 // gn_h[0 .. n_c) = dc_h is copied by workgroup 0.  (Round 1 needed a staging buffer and a second kernel for the per-point sums.)
 #ifndef SATBA_BS_THREADS
 #define SATBA_BS_THREADS 512
@@ -1641,12 +1639,12 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
         }
     }, a.rev);
     double v[3] = {sa, sb, sc};
-    double* const dst[3] = {hdr + 1, hdr + 2, hdr + 3};
+    double* const dst[3] = {hdr + SATBA_HDR_GRAM_A, hdr + SATBA_HDR_GRAM_B, hdr + SATBA_HDR_GRAM_C};
     grid_sum<3>(v, dst, rb);
 }
 
 // ------------------------------------------------------------------------------------------------ subspace / trial vectors
-// q1 = s g_h, w = gn_h - alpha g_h;  hdr[1] = w.w, hdr[2] = w.q1, hdr[6] = g_h.w
+// q1 = s g_h, w = gn_h - alpha g_h;  hdr[SATBA_HDR_WW] = w.w, hdr[SATBA_HDR_WQ1] = w.q1, hdr[SATBA_HDR_GHW] = g_h.w
 __global__ __launch_bounds__(256) void k_subspace_vec(int n, int n_c, double lead, double alpha, double s,
                                                       const double* __restrict__ gh, const double* __restrict__ gn,
                                                       double* __restrict__ q1, double* __restrict__ wv, RedBuf rb,
@@ -1662,7 +1660,7 @@ __global__ __launch_bounds__(256) void k_subspace_vec(int n, int n_c, double lea
         ww += wgt * w * w; wq += wgt * w * q; gw += wgt * h * w;
     }
     double v[3] = {ww, wq, gw};
-    double* const dst[3] = {hdr + 1, hdr + 2, hdr + 6};
+    double* const dst[3] = {hdr + SATBA_HDR_WW, hdr + SATBA_HDR_WQ1, hdr + SATBA_HDR_GHW};
     grid_sum<3>(v, dst, rb);
 }
 

@@ -33,6 +33,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/satba.h"
 #include "satba_lm.h"
 
 namespace satba {
@@ -82,11 +83,6 @@ __host__ __device__ inline long long lm_stamp_value(unsigned long long w) { retu
 __host__ __device__ inline long long lm_summary_tick(unsigned long long w) { return (long long)(w >> 8); }
 __host__ __device__ inline int lm_summary_phase(unsigned long long w) { return (int)(w & 0xff); }
 
-// header slots (satba/trf.py)
-enum { LMH_GRAM_A = 1, LMH_GRAM_B = 2, LMH_GRAM_C = 3, LMH_CHOL_FAIL = 4, LMH_COST_NEW = 1, LMH_STEP_SQ = 2, LMH_X_SQ = 3,
-       LMH_WW = 1, LMH_B11 = 3, LMH_B12 = 4, LMH_B22 = 5, LMH_GHW = 6,
-       LMH_K_COST = 8, LMH_K_GINF = 9, LMH_K_JG_SQ = 11, LMH_K_LAM = 13, LMH_K_DELTA = 14, LMH_FX_BAD = 15 };
-
 // start of a solve: the state comes by value (queued like everything else: no host staging buffer to wait for)
 __global__ void k_lm_reset(LmDev* __restrict__ st, LmDev init, int keep_counters) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -133,21 +129,21 @@ __device__ inline void lm_decide1a(LmDev* __restrict__ gst, const double* __rest
         return;
     }
     // fixed-point overflow of the camera sums: the host switches the summation route and repeats (nothing is booked)
-    if (h[LMH_FX_BAD] != 0.0) { lm_to_host(st, LM_HOST_FX); return; }
-    // the factorisation beside the pair kernel timed out waiting for it (status bit 1: the two kernels did not run at the same time --
+    if (h[SATBA_HDR_FX_BAD] != 0.0) { lm_to_host(st, LM_HOST_FX); return; }
+    // the factorisation beside the pair kernel timed out waiting for it (SATBA_CHOL_TIMEOUT: the two kernels did not run at the same time --
     // launches serialised by a tool, two streams on one hardware queue): not a failed factorisation.  Nothing is booked, the damping
     // stays; the host switches the handle to one kernel after the other and resumes the loop at this front (lm_drive)
-    // (round-5 advisor: only a wait BETWEEN the two kernels -- status bit 2, raised by c3_wait_arrive and k_unscale's spin -- is handed back; a
+    // (round-5 advisor: only a wait BETWEEN the two kernels -- SATBA_CHOL_BESIDE_WAIT, raised by c3_wait_arrive and k_unscale's spin -- is handed back; a
     // time-out inside a sequential front, or with several ranks, is a factorisation that did not finish: the escalation branch below)
-    if (h[LMH_CHOL_FAIL] >= 4.0) { st->resume_lin = st->run_lin; lm_to_host(st, LM_HOST_BESIDE); return; }
+    if (h[SATBA_HDR_CHOL_FAIL] >= (double)SATBA_CHOL_BESIDE_WAIT) { st->resume_lin = st->run_lin; lm_to_host(st, LM_HOST_BESIDE); return; }
     if (st->run_lin) {
         // bookkeeping of the new linearisation (scipy trf.py:536-546 after an accepted step; :405-426 before the loop)
-        const double cost = h[LMH_K_COST];
+        const double cost = h[SATBA_HDR_KEEP + SATBA_KEEP_COST];
         if (st->first && !isfinite(cost)) { lm_to_host(st, LM_HOST_NONFINITE); return; }
         st->cost = cost;
-        st->g_norm = h[LMH_K_GINF];
+        st->g_norm = h[SATBA_HDR_KEEP + SATBA_KEEP_GINF];
         if (st->first) {
-            st->Delta = h[LMH_K_DELTA];
+            st->Delta = h[SATBA_HDR_KEEP + SATBA_KEEP_DELTA];
             st->initial_cost = cost;
             st->nfev = 1; st->njev = 1;
             st->first = 0;
@@ -156,8 +152,8 @@ __device__ inline void lm_decide1a(LmDev* __restrict__ gst, const double* __rest
         }
         st->run_lin = 0;  // booked (a repeated factorisation of the same linearisation must not book it again)
         st->attempts = 0;
-        st->reg = h[LMH_K_LAM];
-        st->jg_sq = h[LMH_K_JG_SQ];
+        st->reg = h[SATBA_HDR_KEEP + SATBA_KEEP_LAM];
+        st->jg_sq = h[SATBA_HDR_KEEP + SATBA_KEEP_JG_SQ];
         // top of the loop (trf.py:450-458)
         if (!st->never_stop) {
             if (st->g_norm < st->gtol) st->status = 1;
@@ -165,7 +161,7 @@ __device__ inline void lm_decide1a(LmDev* __restrict__ gst, const double* __rest
         }
     }
     // a Cholesky needs a floor where LSMR copes with a numerically singular system: escalate the damping and factorise again
-    if (!(h[LMH_CHOL_FAIL] == 0.0) || !isfinite(h[LMH_GRAM_C])) {
+    if (!(h[SATBA_HDR_CHOL_FAIL] == 0.0) || !isfinite(h[SATBA_HDR_GRAM_C])) {
         if (++st->attempts > 10) { lm_to_host(st, LM_HOST_CHOL); return; }
         st->reg = fmax(st->reg, 1e-16) * 100.0;
         st->lam_force = st->reg;
@@ -173,7 +169,7 @@ __device__ inline void lm_decide1a(LmDev* __restrict__ gst, const double* __rest
     }
     st->run_solve = 0;
     st->lam_force = 0.0;
-    const double ga = h[LMH_GRAM_A], gb = h[LMH_GRAM_B], gc = h[LMH_GRAM_C];
+    const double ga = h[SATBA_HDR_GRAM_A], gb = h[SATBA_HDR_GRAM_B], gc = h[SATBA_HDR_GRAM_C];
     st->ga = ga; st->gb = gb; st->gc = gc;
     const double sa = sqrt(ga), alpha = gb / ga;
     st->sa = sa; st->alpha = alpha;
@@ -241,7 +237,7 @@ __global__ void k_lm_decide1b(LmDev* __restrict__ st, const double* __restrict__
     if (st->phase != LM_NEED_SUB || !st->run_sub) return;
     st->phase = LM_RUN;  // the subspace pattern is running: the loop carries on behind it
     st->run_sub = 0;
-    const double ww = h[LMH_WW];
+    const double ww = h[SATBA_HDR_WW];
     if (!(ww > 1e-24 * st->gc && ww > 0)) {  // gn_h parallel to g_h
         st->Ba = st->jg_sq / st->ga; st->Bb = 0.0; st->Bc = 1.0;
         st->gS0 = st->sa; st->gS1 = 0.0;
@@ -249,7 +245,7 @@ __global__ void k_lm_decide1b(LmDev* __restrict__ st, const double* __restrict__
         lm_trial_step(st);
     } else {
         st->nw = sqrt(ww);
-        st->gS1 = h[LMH_GHW] / st->nw;
+        st->gS1 = h[SATBA_HDR_GHW] / st->nw;
         st->Bc = ww;  // parked: |w|^2 for decide1c
         st->run_prod = 1;
     }
@@ -262,7 +258,7 @@ __global__ void k_lm_decide1c(LmDev* __restrict__ st, const double* __restrict__
     if (st->phase != LM_RUN || !st->run_prod) return;
     st->run_prod = 0;
     const double ww = st->Bc;
-    st->Ba = h[LMH_B11]; st->Bb = h[LMH_B12] / st->nw; st->Bc = h[LMH_B22] / ww;
+    st->Ba = h[SATBA_HDR_B11]; st->Bb = h[SATBA_HDR_B12] / st->nw; st->Bc = h[SATBA_HDR_B22] / ww;
     st->gS0 = st->sa;
     st->one_dim = 0;
     lm_trial_step(st);
@@ -338,7 +334,7 @@ __device__ __noinline__ void lm_decide2_body(LmDev* gst, double cost_new_in, dou
 
 __global__ void k_lm_decide2(LmDev* __restrict__ gst, const double* __restrict__ h, LmSummary* __restrict__ sum) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    lm_decide2_body(gst, h[LMH_COST_NEW], h[LMH_STEP_SQ], h[LMH_X_SQ], sum);
+    lm_decide2_body(gst, h[SATBA_HDR_COST_NEW], h[SATBA_HDR_STEP_SQ], h[SATBA_HDR_X_SQ], sum);
 }
 
 // After LM_HOST_BESIDE the host has switched the handle to sequential fronts (and waited for the stream: nothing else touches the

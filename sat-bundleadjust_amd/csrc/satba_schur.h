@@ -23,12 +23,12 @@ constexpr int PV_STRIDE = 16;  // doubles per packed point record: 12 used, padd
 // PV: packed per-point record X(3) | Vinv(6) | g_p(3) for the gather-heavy Schur kernels
 // The copy of Vinv inside PV is multiplied by the point's fixed mask (0 for a frozen point, 1 otherwise): every Schur term
 // contains Vinv_p exactly once, so the Schur kernels need no mask of their own (a gather of perm[] per hit otherwise).
-// Start of satba_schur_auto: the (already all-reduced) prepare header -> keep[1] = |g|_inf, keep[2..4] = |g_h|^2, |J_h g_h|^2,
-// |x_h|^2; trust radius (scipy trf.py:440-442 when Delta <= 0: first iteration) -> keep[6]; damping of the Gauss-Newton system
-// from the Cauchy step (scipy trf.py:473-477, common.py:302-322) -> keep[5].  Returns the damping.  Every thread of k_vinv
+// Start of satba_schur_auto: the (already all-reduced) prepare header -> keep[SATBA_KEEP_GINF] = |g|_inf, keep[SATBA_KEEP_GH_SQ .. _XS_SQ] =
+// |g_h|^2, |J_h g_h|^2, |x_h|^2; trust radius (scipy trf.py:440-442 when Delta <= 0: first iteration) -> keep[SATBA_KEEP_DELTA]; damping of the
+// Gauss-Newton system from the Cauchy step (scipy trf.py:473-477, common.py:302-322) -> keep[SATBA_KEEP_LAM].  Returns the damping.  Every thread of k_vinv
 // evaluates it from the header (a dozen operations; a one-thread kernel in front cost a launch), one thread writes `keep`.
 __device__ inline double schur_lambda(const double* __restrict__ hdr, double Delta, double lam_floor, double* __restrict__ keep, bool write) {
-    const double gh_sq = hdr[1], jg_sq = hdr[2], xs_sq = hdr[3];
+    const double gh_sq = hdr[SATBA_HDR_GH_SQ], jg_sq = hdr[SATBA_HDR_JG_SQ], xs_sq = hdr[SATBA_HDR_XS_SQ];
     if (!(Delta > 0.0)) {
         Delta = sqrt(xs_sq);
         if (Delta == 0.0) Delta = 1.0;
@@ -43,10 +43,10 @@ __device__ inline double schur_lambda(const double* __restrict__ hdr, double Del
     double lam = -best / (Delta * Delta);
     if (!(lam >= lam_floor)) lam = lam_floor;  // also catches NaN (zero gradient)
     if (write) {
-        keep[1] = fmax(keep[1], hdr[4]);
-        keep[2] = gh_sq; keep[3] = jg_sq; keep[4] = xs_sq;
-        keep[5] = lam;
-        keep[6] = Delta;
+        keep[SATBA_KEEP_GINF] = fmax(keep[SATBA_KEEP_GINF], hdr[SATBA_HDR_GC_INF]);
+        keep[SATBA_KEEP_GH_SQ] = gh_sq; keep[SATBA_KEEP_JG_SQ] = jg_sq; keep[SATBA_KEEP_XS_SQ] = xs_sq;
+        keep[SATBA_KEEP_LAM] = lam;
+        keep[SATBA_KEEP_DELTA] = Delta;
     }
     return lam;
 }
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(VINV_THREADS) void k_vinv(int N, double lam, const 
     if (lam_force && *lam_force > 0.0) {  // ... and so does the escalated damping after a failed factorisation (the prepare header is gone then)
         hdr_auto = nullptr;
         lam = *lam_force;
-        if (blockIdx.x == 0 && threadIdx.x == 0) keep[5] = lam;
+        if (blockIdx.x == 0 && threadIdx.x == 0) keep[SATBA_KEEP_LAM] = lam;
     }
     __shared__ double2 s_t[VINV_THREADS / 64][64 * 9];  // per wave: 64 records x 144 bytes (the Vinv rows use the front of it)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -185,7 +185,7 @@ struct SchurArgs {
     // ... with point-range chunks (weighted / robust runs): every (pair, chunk) item publishes its partial block and counts itself in
     // pair_cnt[pair] (n_pairs ints, zero between launches); the item of the LAST chunk -- the last of its pair in dispatch order: every
     // other one has been started before it -- waits for that count, adds the partials in chunk order (k_schur_finish's arithmetic),
-    // publishes the block and counts the pair in `arrive`.  fail: the factorisation's status word (bit 1: a wait timed out)
+    // publishes the block and counts the pair in `arrive`.  fail: the factorisation's status word (SATBA_CHOL_TIMEOUT: a wait timed out)
     int* pair_cnt = nullptr;
     int* fail = nullptr;
 };
@@ -260,7 +260,7 @@ __device__ __forceinline__ void schur_pair_publish(double* mine, size_t stride, 
         int spins = 0;
         while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n_chunks - 1) {
             __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1 << 22)) { atomicOr(fail, 2); break; }
+            if (++spins > (1 << 22)) { atomicOr(fail, SATBA_CHOL_TIMEOUT); break; }
         }
         __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -387,7 +387,7 @@ __device__ __forceinline__ void schur_pairs_epilogue_wide(const ObsArgs& a, cons
             int spins = 0;
             while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < s.n_chunks - 1) {
                 __builtin_amdgcn_s_sleep(4);
-                if (++spins > (1 << 22)) { atomicOr(s.fail, 2); break; }
+                if (++spins > (1 << 22)) { atomicOr(s.fail, SATBA_CHOL_TIMEOUT); break; }
             }
             __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -479,7 +479,7 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
                 const long long t0 = wall_clock64();
                 while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < s.n_dg - 1) {
                     __builtin_amdgcn_s_sleep(4);
-                    if (wall_clock64() - t0 > 100000000ll) { atomicOr(s.fail, 2); break; }  // (1 s: a workgroup of this launch never ran)
+                    if (wall_clock64() - t0 > 100000000ll) { atomicOr(s.fail, SATBA_CHOL_TIMEOUT); break; }  // (1 s: a workgroup of this launch never ran)
                 }
                 __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) void 
 //                          chunk order: repeatable
 // Every block of the lower triangle is written by a kernel of the Schur phase (the off-diagonal ones here or by k_schur_pairs, also for
 // pairs without a common point), so S is not cleared first (an 8 MB fill per iteration at 200 cameras x 5); the strict upper triangle is
-// never read.  lam_dev (optional): the damping is read from device memory (keep[5], written by k_vinv) instead of the argument.
+// never read.  lam_dev (optional): the damping is read from device memory (keep[SATBA_KEEP_LAM], written by k_vinv) instead of the argument.
 // rhs_scaled (or null): every entry of S passes through this launch and the dense solve follows at once (one rank): the system goes out in
 // scaled variables -- S / (scale_inv_r scale_inv_c), rhs_scaled = rhs / scale_inv, k_scale_system's arithmetic -- and the solver's
 // status word and flags (n_clear ints at clear) are cleared: that launch is gone, too.

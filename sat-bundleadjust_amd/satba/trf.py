@@ -41,7 +41,7 @@ import os
 
 import numpy as np
 
-# header slots, per phase (the header is zeroed by each phase before it writes)
+# header slots, per phase (the header is zeroed by each phase before it writes); include/satba.h: SATBA_HDR_*, the same values
 COST = 0
 GH_SQ, JG_SQ, XS_SQ, GC_INF = 1, 2, 3, 4
 GRAM_A, GRAM_B, GRAM_C, CHOL_FAIL = 1, 2, 3, 4
@@ -352,6 +352,26 @@ def _print_iteration(iteration, nfev, cost, cost_reduction, step_norm, optimalit
     print(f"{iteration:^15}{nfev:^15}{cost:^15.4e}{cr}{sn}{optimality:^15.2e}")
 
 
+def _report(res, verbose):
+    """scipy's final two-line report (verbose >= 1); returns res."""
+    if verbose >= 1:
+        print(res.message)
+        print("Function evaluations {}, initial cost {:.4e}, final cost {:.4e}, first-order optimality {:.2e}."
+              .format(res.nfev, res.initial_cost, res.cost, res.optimality))
+    return res
+
+
+def _exchange_and_solve(engine, comm, lm_part=None):
+    """Sum the reduced system over the ranks and solve it: in messages (TorchComm.solve_in_messages), else in one piece.  lm_part: as there."""
+    if getattr(comm, "solve_in_messages", None) and comm.solve_in_messages(engine, lm_part):
+        return
+    comm.allreduce_schur(engine)
+    if lm_part is None:
+        engine.solve()
+    else:
+        lm_part(3)
+
+
 def subspace_model(engine, exchange, ga, gb, gc, jg_sq, reg):
     """
     Quadratic model on the orthonormal basis {q1, q2} = {g_h / |g_h|, w / |w|}, w = gn_h - (b / a) g_h, of
@@ -419,9 +439,7 @@ def drive_device_loop(engine, comm, lam_floor=0.0, max_patterns=None, watchdog_s
         engine.lm_part(1)
         comm.allreduce(engine, hdr)
         engine.lm_part(2, lam_floor)
-        if not (getattr(comm, "solve_in_messages", None) and comm.solve_in_messages(engine, engine.lm_part)):
-            comm.allreduce_schur(engine)
-            engine.lm_part(3)
+        _exchange_and_solve(engine, comm, engine.lm_part)
         comm.allreduce(engine, hdr)
         engine.lm_part(4)
         comm.allreduce(engine, hdr)
@@ -489,14 +507,9 @@ def trf_solve(engine, comm=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=None,
         native = comm.world == 1 and not getattr(comm, "always", False) and verbose < 2 and hasattr(engine, "solve_lm") and timers is None
     if native:
         st = engine.solve_lm(ftol=ftol, xtol=xtol, gtol=gtol, max_nfev=max_nfev, loss=loss, f_scale=f_scale, verbose=0)
-        res = Result(cost=st.cost, optimality=st.optimality, nfev=int(st.nfev), njev=int(st.njev), status=int(st.status),
-                     success=st.status > 0, message=TERMINATION_MESSAGES[int(st.status)], iterations=int(st.iterations),
-                     initial_cost=st.initial_cost)
-        if verbose >= 1:
-            print(res.message)
-            print("Function evaluations {}, initial cost {:.4e}, final cost {:.4e}, first-order optimality {:.2e}."
-                  .format(res.nfev, res.initial_cost, res.cost, res.optimality))
-        return res
+        return _report(Result(cost=st.cost, optimality=st.optimality, nfev=int(st.nfev), njev=int(st.njev), status=int(st.status),
+                              success=st.status > 0, message=TERMINATION_MESSAGES[int(st.status)], iterations=int(st.iterations),
+                              initial_cost=st.initial_cost), verbose)
     if isinstance(comm, TorchComm) and (comm.world > 1 or comm.always) and hasattr(engine, "use_torch_stream"):
         engine.use_torch_stream()  # the all-reduces are queued on torch's stream: the phases must order with them
         # several ranks: the decisions of the loop on the device, the host only queues (no header read inside an iteration);
@@ -506,11 +519,7 @@ def trf_solve(engine, comm=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=None,
             engine.configure(loss, f_scale)
             res, dev_state = trf_solve_sharded(engine, comm, ftol, xtol, gtol, max_nfev, loss, f_scale)
             if res is not None:
-                if verbose >= 1:
-                    print(res.message)
-                    print("Function evaluations {}, initial cost {:.4e}, final cost {:.4e}, first-order optimality {:.2e}."
-                          .format(res.nfev, res.initial_cost, res.cost, res.optimality))
-                return res
+                return _report(res, verbose)
             # the device handed over (all ranks stop for the same reason: it follows from all-reduced headers)
             reason = int(dev_state["host_reason"])
             if reason == LM_HOST_NONFINITE:
@@ -547,9 +556,7 @@ def trf_solve(engine, comm=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=None,
             engine.prepare(Delta is None)
             comm.allreduce(engine, hdr)
             engine.schur_auto(-1.0 if Delta is None else Delta, 0.0)
-            if not (getattr(comm, "solve_in_messages", None) and comm.solve_in_messages(engine)):
-                comm.allreduce_schur(engine)
-                engine.solve()
+            _exchange_and_solve(engine, comm)
             h = exchange(hdr)
             # K_FX_BAD (summed over the ranks): a term of some shard's fixed-point camera sums left its range -- every rank
             # switches to the camera-major sums and repeats the iteration (include/satba.h, SATBA_HDR_FX_BAD)
@@ -599,9 +606,7 @@ def trf_solve(engine, comm=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=None,
                 break
             reg = max(reg, 1e-16) * 100.0
             engine.schur(reg)
-            if not (getattr(comm, "solve_in_messages", None) and comm.solve_in_messages(engine)):
-                comm.allreduce_schur(engine)
-                engine.solve()
+            _exchange_and_solve(engine, comm)
             h = exchange(hdr)
         else:
             raise RuntimeError("reduced camera system could not be factorised")
@@ -647,10 +652,5 @@ def trf_solve(engine, comm=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=None,
 
     if status is None:
         status = 0
-    res = Result(cost=cost, optimality=g_norm, nfev=nfev, njev=njev, status=status, success=status > 0,
-                 message=TERMINATION_MESSAGES[status], iterations=lm_iterations, initial_cost=initial_cost)
-    if verbose >= 1:
-        print(res.message)
-        print("Function evaluations {}, initial cost {:.4e}, final cost {:.4e}, first-order optimality {:.2e}."
-              .format(nfev, initial_cost, cost, g_norm))
-    return res
+    return _report(Result(cost=cost, optimality=g_norm, nfev=nfev, njev=njev, status=status, success=status > 0,
+                          message=TERMINATION_MESSAGES[status], iterations=lm_iterations, initial_cost=initial_cost), verbose)

@@ -90,6 +90,18 @@ def test_c_abi_library_exports_every_declared_symbol():
         assert hasattr(lib, sym), sym
     assert lib.satba_version() >= 1
     assert engine_hip.HDR_FIXED == int(re.search(r"#define SATBA_HDR_FIXED (\d+)", header).group(1))
+    # one table of header slots: every name of satba/trf.py is the header's #define of the same name
+    defs = {name: int(value) for name, value in re.findall(r"^#define SATBA_(\w+) (\d+)\b", header, re.M)}
+    from satba import trf
+
+    for name in ("COST", "GH_SQ", "JG_SQ", "XS_SQ", "GC_INF", "GRAM_A", "GRAM_B", "GRAM_C", "CHOL_FAIL", "WW", "WQ1", "B11", "B12", "B22", "GHW",
+                 "COST_NEW", "STEP_SQ", "X_SQ"):
+        assert getattr(trf, name) == defs["HDR_" + name], name
+    kept = ("COST", "GINF", "GH_SQ", "JG_SQ", "XS_SQ", "LAM", "DELTA", "FX_BAD")
+    assert len(kept) == defs["KEEP_LEN"] and defs["HDR_KEEP"] + defs["KEEP_LEN"] <= defs["HDR_FIXED"]
+    for offset, name in enumerate(kept):
+        assert defs["KEEP_" + name] == offset and getattr(trf, "K_" + name) == defs["HDR_KEEP"] + offset, name
+    assert trf.K_FX_BAD == defs["HDR_FX_BAD"]
     from satba import rpc_model
 
     assert rpc_model.RPC_TABLE_LEN == int(re.search(r"#define SATBA_RPC_TABLE_LEN (\d+)", header).group(1))
