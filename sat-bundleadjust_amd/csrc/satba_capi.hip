@@ -32,6 +32,7 @@
 #include "satba_rpcfit.h"
 #include "satba_camapprox.h"
 #include "satba_schur.h"
+#include "satba_schur_items.h"
 
 #include <dlfcn.h>
 
@@ -82,6 +83,9 @@ static int fail(int code, const char* fmt, ...) {
     } while (0)
 
 constexpr int RED_SLOTS = 8, RED_MAX_GRID = 2048, RED_MAX_NV = 4;
+// an item table of k_schur_pairs on the device: the items in dispatch order (satba_schur_items.h), the same flattened (k_schur_item_desc), workgroups of 4 items
+struct SchurItems { int2* items = nullptr; SchurItem* desc = nullptr; int n_blocks = 0; };
+static_assert(sizeof(SchurItemKey) == sizeof(int2) && offsetof(SchurItemKey, pair) == offsetof(int2, x) && offsetof(SchurItemKey, chunk) == offsetof(int2, y), "uploaded as int2");
 
 struct satba_problem {
     int model = 0, M = 0, N = 0, NP = 0, c_p = 0, n_cam_fix = 0, n_pts_fix = 0, rank = 0, world = 1, f32 = 0, device = 0;
@@ -123,18 +127,12 @@ struct satba_problem {
     size_t prof_used = 0;
     double* d_Jpm = nullptr;                  // RPC: Jacobian blocks of the current linearisation, io order
     double *d_part = nullptr, *d_part3 = nullptr, *d_pair_part = nullptr;
-    int2* d_items = nullptr;  // (pair, chunk) work items of the Schur pair kernel in dispatch order
-    SchurItem* d_item_desc = nullptr;
+    SchurItems items_chunked;  // (pair, chunk) work items of the Schur pair kernel
+    SchurItems items_merged;   // one item per pair (all chunks), for the unit-weight kernels (schur_item_tables: not on every handle)
     // weighted / robust runs of the affine and perspective models (Layout::w_fix, built on first use by ensure_wlayout): the merged
     // records W and the item table with the diagonal items in front of every (camera row, chunk) group
     double2* d_W = nullptr;
-    int2* d_items_w = nullptr;
-    SchurItem* d_item_desc_w = nullptr;
-    int n_item_blocks_w = 0;
-    int2* d_items_merged = nullptr;           // one item per pair (all chunks), for the unit-weight kernels
-    SchurItem* d_item_desc_merged = nullptr;
-    int n_item_blocks_merged = 0;
-    int n_item_blocks = 0;
+    SchurItems items_w;
     int lin_grid = 0, cm_chunks = 1, cm_chunks_w = 1;  // chunks of the camera-major passes (unit weights and k_cam_sums | weighted / robust k_schur_diag)
     double* d_red = nullptr;  // RED_SLOTS x (RED_MAX_NV x RED_MAX_GRID doubles) partials of the deterministic grid sums
     unsigned* d_red_cnt = nullptr;
@@ -254,7 +252,10 @@ static int dev_alloc(satba_problem* p, T** out, size_t count) {
     } while (0)
 
 // weighted / robust runs with recomputed Jacobians (affine, perspective): row scales and point records share the merged records W
-static bool wmode(const satba_problem* p) { return p->model != RPC && !(p->loss == 0 && p->unit_weights); }
+static bool unit_run(const satba_problem* p) { return p->loss == 0 && p->unit_weights; }  // every weight is 1 and the loss is linear
+static bool wmode(const satba_problem* p) { return p->model != RPC && !unit_run(p); }
+static bool merged_records(const satba_problem* p) { return wmode(p) && p->L.wl_ready; }  // ... and their layout is built: the kernels work on W
+static bool pairs_run(const satba_problem* p) { return p->L.n_pairs > 0 && p->L.E > 0; }  // two cameras share a point: a Schur pair kernel runs
 
 static ObsArgs obs_args(const satba_problem* p, bool at_new, const int* gate = nullptr) {
     ObsArgs a;
@@ -266,14 +267,14 @@ static ObsArgs obs_args(const satba_problem* p, bool at_new, const int* gate = n
     a.rpc = p->d_rpc;
     a.Jpm = at_new ? nullptr : p->d_Jpm;  // stored Jacobian blocks belong to the linearisation at x
     a.sc = nullptr;  // (RPC: the row scales ride in the stored D', ObsEval::store_jac)
-    if (wmode(p)) {  // the scales live in W: sc_ofs[q] + k instead of ipt_ofs[q] + k (null until the first linearisation has built the layout)
-        a.sc = (at_new || !L.wl_ready) ? nullptr : p->d_W;
-        if (L.wl_ready) a.ipt_ofs = L.sc_ofs;
+    if (merged_records(p)) {  // the scales live in W: sc_ofs[q] + k instead of ipt_ofs[q] + k (null until the first linearisation has built the layout)
+        a.sc = at_new ? nullptr : p->d_W;
+        a.ipt_ofs = L.sc_ofs;
     }
     a.K = p->K; a.P = L.P; a.n_slices = L.n_slices; a.M = p->M; a.N = p->N; a.n_c = p->n_c;
     a.n_cam_fix = p->n_cam_fix; a.n_pts_fix = p->n_pts_fix; a.loss = p->loss; a.f32 = p->f32;
     a.f_scale = p->f_scale;
-    a.unit = (p->loss == 0 && p->unit_weights) ? 1 : 0;
+    a.unit = unit_run(p) ? 1 : 0;
     a.rep_shift = p->lin_rep_shift;
     a.fxe = p->d_fxe; a.fx_flag = p->d_fxflag; a.gate = gate;
     a.prep_scale = nullptr; a.prep_gh = nullptr; a.prep_ghs = nullptr; a.prep_first_dev = nullptr; a.prep_first = 0;
@@ -281,8 +282,9 @@ static ObsArgs obs_args(const satba_problem* p, bool at_new, const int* gate = n
     a.sh = 0;  // lanes per point: set by the launchers of the kernels that support it
     return a;
 }
-static CamMajor cam_major(const satba_problem* p) {
-    return CamMajor{p->L.cam_ofs, p->L.cm_pt, p->L.cm_pos, (wmode(p) && p->L.wl_ready) ? p->L.cm_sc : p->L.cm_io};
+// pt_rec: k_schur_diag on the merged records (SchurRoute::cm_rec) -- piece offsets instead of point indices
+static CamMajor cam_major(const satba_problem* p, bool pt_rec = false) {
+    return CamMajor{p->L.cam_ofs, pt_rec ? p->L.cm_rec : p->L.cm_pt, p->L.cm_pos, merged_records(p) ? p->L.cm_sc : p->L.cm_io};
 }
 
 static int grid_for(long long work, int block, int cap) {
@@ -330,7 +332,7 @@ static int slice_split(const satba_problem* p) {
     // weighted / robust runs: at least two lanes per point at every size (their linearize kernel keeps one record in flight instead of
     // two and sits at its register limit).  200 x 1M x 10M, soft_l1, LM it/s: 1 lane 455 / 455 / 455, 2 lanes 467 / 468 / 468, 4 lanes 459;
     // unit weights + linear loss: 841 / 822
-    if (!(p->loss == 0 && p->unit_weights)) sh = std::max(sh, 1);
+    if (!unit_run(p)) sh = std::max(sh, 1);
     return sh;
 }
 // grid of k_linearize: one workgroup per CU (its LDS table is flushed once per workgroup; d_part holds 512 partial tables).  Depends on
@@ -359,7 +361,7 @@ static int launch_residual(satba_problem* p, bool at_new, double2* f, double* co
     const int grid = slice_grid(p, RES_THREADS / 64, 2, a.sh);
     const size_t lds = table_bytes(p);
     const TrialArgs t{};
-    if (p->loss == 0 && p->unit_weights)
+    if (unit_run(p))
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_residual<MODEL, NP, CL, RL, true, false>), dim3(grid), dim3(RES_THREADS), lds, p->stream, a, f, p->red(RB_RES), cost, t));
     else
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_residual<MODEL, NP, CL, RL, false, false>), dim3(grid), dim3(RES_THREADS), lds, p->stream, a, f, p->red(RB_RES), cost, t));
@@ -385,7 +387,7 @@ static int launch_trial(satba_problem* p, const PhaseCtx& c, double c0, double c
     if (c.decide2_in_trial) { t.lm_st = p->d_lm; t.lm_sum = p->h_lm_dev; }  // (lm_launch_tail: one rank, device-resident loop)
     p->fxcost_new_valid = true;
     double* cost = p->d_xb + SATBA_HDR_COST_NEW;
-    if (p->loss == 0 && p->unit_weights)
+    if (unit_run(p))
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_residual<MODEL, NP, CL, RL, true, true>), dim3(grid), dim3(RES_THREADS), lds, p->stream, a, (double2*)nullptr, p->red(RB_RES), cost, t));
     else
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_residual<MODEL, NP, CL, RL, false, true>), dim3(grid), dim3(RES_THREADS), lds, p->stream, a, (double2*)nullptr, p->red(RB_RES), cost, t));
@@ -491,88 +493,19 @@ static int launch_cam_sums(satba_problem* p, const int* gate, double* U, double*
     return 0;
 }
 
-static SchurArgs schur_args(const satba_problem* p) {
-    SchurArgs s;
-    s.PV = reinterpret_cast<const double2*>(p->d_PV);
-    s.pair_ofs = p->L.pair_ofs; s.pair_pts = p->L.pair_pts; s.pair_pi = p->L.pair_pi; s.pair_pj = p->L.pair_pj;
-    s.pair_ij = p->L.pair_ij; s.pair_part = p->d_pair_part; s.n_chunks = p->L.C; s.items = p->d_items; s.desc = p->d_item_desc;
-    if (wmode(p) && p->L.wl_ready) {
-        s.PV = p->d_W; s.wmode = 1; s.zero_fix = p->L.zero_fix; s.n_dg = p->L.n_dg;
-        s.pair_rec = p->L.pair_rec; s.pair_kk = p->L.pair_kk; s.cm_rec = p->L.cm_rec; s.cm_sc = p->L.cm_sc; s.dg_part = p->d_part3;
-        s.items = p->d_items_w; s.desc = p->d_item_desc_w;
-    }
-    return s;
-}
-
-template <int MODEL, int NP>
-static int launch_schur(satba_problem* p, const FrontCtx& f, const ObsArgs& a, double* S, double* rhs) {
-    CamMajor cm = cam_major(p);
-    SchurArgs s = schur_args(p);
-    const long long n_pairs = p->L.n_pairs;
-    // diagonal blocks (with J_c^T J_c) and right-hand side: a camera-major pass of its own -- or, weighted / robust runs on the merged
-    // records, items of the pair kernel in front of every (camera row, chunk) group, whose pair items then find the records in L2
-    const bool pairs_run = n_pairs > 0 && p->L.E > 0;
-    const bool dg_in_pairs = s.wmode && MODEL != RPC && pairs_run;
-    int dchunks = (a.sc && MODEL != RPC) ? p->cm_chunks_w : p->cm_chunks;
-    // the factorisation BEHIND the Schur kernels (no arrival protocol): the diagonal pass and the pair kernel in one launch (k_schur_both)
-    static const bool one_launch_env = !(getenv("SATBA_SCHUR_ONE_LAUNCH") && atoi(getenv("SATBA_SCHUR_ONE_LAUNCH")) == 0);
-    const bool both = one_launch_env && !f.arrive_epoch && !dg_in_pairs && pairs_run;
-    if (dg_in_pairs) dchunks = p->L.n_dg;
-    else {
-        if (s.wmode) cm.pt = p->L.cm_rec;  // (k_schur_diag on the merged records: piece offsets instead of point indices)
-        s.diag_xcd = (dchunks % 8 == 0 && !getenv("SATBA_NO_DIAG_XCD")) ? 1 : 0;
-        if (!both) hipLaunchKernelGGL((k_schur_diag<MODEL, NP>), dim3(p->M, dchunks), dim3(LINC_THREADS), 0, p->stream, a, cm, s, p->d_part3);
-    }
-    const int total = p->M * cam_acc_len(NP);
-    const int nb_diag = (int)((std::max<long long>(8ll * total, p->hdr) + 255) / 256);
-    // end of the phase: diagonal blocks, right-hand side, header (and the pairs' chunk partials, red_chunks > 1) in one launch
-    auto finish = [&](int red_chunks, bool direct) {  // direct: the pair kernel writes (has written) blocks of S itself
-        const long long outs = red_chunks > 1 ? n_pairs * NP * NP : 0;
-        const bool scale = f.scale_in_finish && !direct && 1 + CH_MAX_STEPS <= nb_diag * 256;
-        hipLaunchKernelGGL(k_schur_finish, dim3((unsigned)(nb_diag + (outs + 255) / 256)), dim3(256), 0, p->stream, p->M, NP, p->n_c, dchunks, p->d_part3,
-                           f.lam, f.lam_dev, p->lead, p->d_gc, p->d_scale_inv, S, rhs, p->d_xb, (int)p->hdr, nb_diag, red_chunks,
-                           p->L.pair_ij, p->d_pair_part, a.gate, scale ? p->d_dch : (double*)nullptr, scale ? p->d_fail : (int*)nullptr,
-                           scale ? 1 + CH_MAX_STEPS : 0);
-        p->s_scaled = scale;
-    };
-    if (f.arrive_epoch) {  // the factorisation waits beside this stream: diagonal blocks and right-hand side first, the pair kernel counts its items in
-        if (dg_in_pairs) {  // ... or they come out of the pair kernel as well (SchurArgs::dg_cnt): only the header is cleared here
-            const int keep = dchunks;
-            dchunks = 0;
-            finish(1, true);
-            dchunks = keep;
-            s.dg_cnt = p->d_dg_cnt; s.dg_lam = f.lam; s.dg_lam_dev = f.lam_dev; s.dg_lead = p->lead; s.dg_gc = p->d_gc;
-            s.dg_scale_inv = p->d_scale_inv; s.dg_rhs = rhs;
-        } else finish(1, true);
-        s.arrive = p->d_arrive; s.arrive_epoch = f.arrive_epoch; s.pair_cnt = p->d_pair_cnt; s.fail = p->d_fail;
-    }
-    int red_chunks = 1;
-    if (n_pairs > 0 && p->L.E > 0) {
-        const bool merged = a.unit && p->d_item_desc_merged;  // one item per pair: straight into S, no partials
-        if (merged) { s.desc = p->d_item_desc_merged; s.items = p->d_items_merged; s.n_chunks = 1; }
-        const dim3 igrid((unsigned)(merged ? p->n_item_blocks_merged : (s.wmode ? p->n_item_blocks_w : p->n_item_blocks)));
-        if (both) {
-            const int n_diag = p->M * dchunks, n_diag_pad = (n_diag + 7) & ~7;
-            const dim3 bgrid(igrid.x + (unsigned)n_diag_pad);
-            if (a.unit) hipLaunchKernelGGL((k_schur_both<MODEL, NP, true>), bgrid, dim3(256), 0, p->stream, a, cm, s, p->d_part3, S, n_diag, n_diag_pad, p->M, dchunks);
-            else hipLaunchKernelGGL((k_schur_both<MODEL, NP, false>), bgrid, dim3(256), 0, p->stream, a, cm, s, p->d_part3, S, n_diag, n_diag_pad, p->M, dchunks);
-        }
-        else if (a.unit) hipLaunchKernelGGL((k_schur_pairs<MODEL, NP, true>), igrid, dim3(256), 0, p->stream, a, s, S);
-        else hipLaunchKernelGGL((k_schur_pairs<MODEL, NP, false>), igrid, dim3(256), 0, p->stream, a, s, S);
-        HIP_TRY(hipGetLastError());
-        if (p->L.C > 1 && !merged) red_chunks = p->L.C;
-        if (f.arrive_epoch && (a.unit ? red_chunks > 1 : false)) return fail(SATBA_E_STATE, "factorisation beside a unit-weight pair kernel with chunk partials");
-    }
-    if (!f.arrive_epoch) finish(red_chunks, n_pairs > 0 && p->L.E > 0 && red_chunks == 1);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static int launch_schur_kernel(satba_problem* p, const int* gate, const FrontCtx& f) {
+// The host side of the Schur phase is satba_schur_api.inc; what the code in front of it needs of it.  launch_schur_kernel stays here: its
+// dispatch is the first use of the Schur kernels, and a kernel's place in the code object follows the place of its first use.
+namespace {
+struct SchurRoute;
+int schur_items_build(satba_problem* p, SchurTable kind, SchurItems* t, long long dg_weight);
+int schur_item_tables(satba_problem* p);
+template <int MODEL, int NP> int launch_schur(satba_problem* p, const FrontCtx& f, const SchurRoute& r, const ObsArgs& a, double* S, double* rhs);
+}  // namespace
+static int launch_schur_kernel(satba_problem* p, const int* gate, const FrontCtx& f, const SchurRoute& r) {
     ObsArgs a = obs_args(p, false, gate);
     double* S = p->payload();
     double* rhs = S + (size_t)p->n_c * p->n_c;
-    SATBA_DISPATCH(p, TRY((launch_schur<MODEL, NP>(p, f, a, S, rhs))));
+    SATBA_DISPATCH(p, TRY((launch_schur<MODEL, NP>(p, f, r, a, S, rhs))));
     return 0;
 }
 
@@ -649,92 +582,6 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// ---------------------------------------------------------------------------------------------------- Schur work items
-// Dispatch order of the (pair, chunk) items of k_schur_pairs (see the kernel's comment).  The rows of the pair triangle
-// (all pairs (i, j > i) of one camera i) are dealt to the 8 XCDs longest-first onto the least loaded one; an XCD's items
-// are ordered row by row, chunk by chunk; workgroup b = 8 s + x takes the s-th group of 4 items of XCD x.
-// merged: one item per pair covering all its chunks (chunk = -1 in the table): the unit-weight kernels gather nothing per
-// observation and are faster with four times fewer, longer items (0.548 vs 0.576 ms at 200 x 1M x 10M) -- the weighted / robust
-// kernels are not (their row-scale gathers want the locality of the point-range chunks: 1.58 vs 1.74 ms with two chunks).
-static int schur_item_table_build(satba_problem* p, bool merged, int2** d_items, SchurItem** d_desc, int* n_blocks) {
-    const int M = p->M, C = merged ? 1 : p->L.C, X = 8;
-    std::vector<int2> table;
-    auto item = [&](long long pr, int ch) { return make_int2((int)pr, merged ? -1 : ch); };
-    {
-        std::vector<std::vector<int2>> per(X);
-        std::vector<long long> load(X, 0);
-        for (int i = 0; i + 1 < M; ++i) {  // rows by decreasing length: i ascending
-            int x = 0;
-            for (int k = 1; k < X; ++k) if (load[k] < load[x]) x = k;
-            load[x] += M - 1 - i;
-            for (int ch = 0; ch < C; ++ch) {
-                for (int j = i + 1; j < M; ++j) per[x].push_back(item(pair_index(M, i, j), ch));
-                while (per[x].size() % 4) per[x].push_back(make_int2(-1, 0));  // a workgroup stays inside one (row, chunk) group
-            }
-        }
-        size_t slots = 0;
-        for (int x = 0; x < X; ++x) slots = std::max(slots, per[x].size() / 4);
-        table.assign(slots * X * 4, make_int2(-1, 0));
-        for (int x = 0; x < X; ++x)
-            for (size_t s = 0; s < per[x].size() / 4; ++s)
-                for (int w = 0; w < 4; ++w) table[(s * X + x) * 4 + w] = per[x][s * 4 + w];
-    }
-    if (table.empty()) table.push_back(make_int2(-1, 0)), table.resize(4, make_int2(-1, 0));
-    *n_blocks = (int)(table.size() / 4);
-    TRY(dev_alloc(p, d_items, table.size()));
-    HIP_TRY(hipMemcpy(*d_items, table.data(), sizeof(int2) * table.size(), hipMemcpyHostToDevice));
-    TRY(dev_alloc(p, d_desc, table.size()));
-    hipLaunchKernelGGL(k_schur_item_desc, dim3((unsigned)((table.size() + 255) / 256)), dim3(256), 0, p->stream, (long long)table.size(), *d_items,
-                       p->L.pair_ij, p->L.pair_ofs, p->L.C, *d_desc);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static int schur_item_table(satba_problem* p) {
-    TRY(schur_item_table_build(p, false, &p->d_items, &p->d_item_desc, &p->n_item_blocks));
-    const char* mg = getenv("SATBA_SCHUR_MERGE");  // experiments: 0 keeps the chunked items for every kernel
-    // ... where the pairs alone fill the chip: with few cameras the chunks are what provides the parallelism (50 cameras: 1 225 pairs)
-    const bool enough = p->L.n_pairs >= 8192 || (mg && atoi(mg) != 0);
-    if (p->L.C > 1 && enough && !(mg && atoi(mg) == 0)) TRY(schur_item_table_build(p, true, &p->d_items_merged, &p->d_item_desc_merged, &p->n_item_blocks_merged));
-    return 0;
-}
-
-// Item table of the weighted / robust pair kernel on the merged records: as above (chunked items, rows dealt to the XCDs), with the
-// diagonal items of (camera i, chunk) -- dg_spc of them, one wave each over an equal share of the camera's entries in the chunk -- in
-// FRONT of the pair items (i, j > i) of that chunk: they pull the chunk's records of camera i into the XCD's L2, where the pair items
-// then find them.  The last camera has no pair items: its diagonal items form groups of their own.
-static int schur_item_table_w(satba_problem* p) {
-    const int M = p->M, C = p->L.C, X = 8, spc = p->L.dg_spc;
-    std::vector<std::vector<int2>> per(X);
-    std::vector<long long> load(X, 0);
-    const long long dg_weight = std::max<long long>(1, p->L.n_pairs > 0 && p->L.E > 0 ? (long long)((double)p->K / M / ((double)p->L.E / p->L.n_pairs)) : 1);
-    for (int i = 0; i < M; ++i) {
-        int x = 0;
-        for (int k = 1; k < X; ++k) if (load[k] < load[x]) x = k;
-        load[x] += (M - 1 - i) + dg_weight;
-        for (int ch = 0; ch < C; ++ch) {
-            for (int sub = 0; sub < spc; ++sub) per[x].push_back(make_int2(-2 - i, ch * spc + sub));
-            for (int j = i + 1; j < M; ++j) per[x].push_back(make_int2((int)pair_index(M, i, j), ch));
-            while (per[x].size() % 4) per[x].push_back(make_int2(-1, 0));
-        }
-    }
-    size_t slots = 0;
-    for (int x = 0; x < X; ++x) slots = std::max(slots, per[x].size() / 4);
-    std::vector<int2> table(std::max<size_t>(slots, 1) * X * 4, make_int2(-1, 0));
-    for (int x = 0; x < X; ++x)
-        for (size_t sl = 0; sl < per[x].size() / 4; ++sl)
-            for (int w = 0; w < 4; ++w) table[(sl * X + x) * 4 + w] = per[x][sl * 4 + w];
-    p->n_item_blocks_w = (int)(table.size() / 4);
-    TRY(dev_alloc(p, &p->d_items_w, table.size()));
-    HIP_TRY(hipMemcpyAsync(p->d_items_w, table.data(), sizeof(int2) * table.size(), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));  // (the host vector goes away)
-    TRY(dev_alloc(p, &p->d_item_desc_w, table.size()));
-    hipLaunchKernelGGL(k_schur_item_desc, dim3((unsigned)((table.size() + 255) / 256)), dim3(256), 0, p->stream, (long long)table.size(), p->d_items_w,
-                       p->L.pair_ij, p->L.pair_ofs, p->L.C, p->d_item_desc_w, p->L.dg_ofs, p->L.n_dg);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // The merged record layout of the weighted / robust runs (Layout::w_fix), built when the first such linearisation is queued: record
 // offsets from the track lengths (one scan), the pair and camera-major lists re-expressed as piece offsets, the diagonal items.
 static int ensure_wlayout(satba_problem* p) {
@@ -788,7 +635,9 @@ static int ensure_wlayout(satba_problem* p) {
         TRY(dev_alloc(p, &L.dg_ofs, (size_t)M * L.n_dg + 1));
         hipLaunchKernelGGL(k_lay_diag_items, dim3((unsigned)((M * C + 1 + 255) / 256)), dim3(256), 0, st, M, C, spc, std::max(N, 1), L.cam_ofs, L.cm_pt, L.dg_ofs);
         HIP_TRY(hipGetLastError());
-        TRY(schur_item_table_w(p));
+        // what a camera's diagonal items weigh when the rows are dealt to the XCDs, in pair items: its entries over those of a pair
+        const long long dg_weight = std::max<long long>(1, pairs_run(p) ? (long long)((double)p->K / M / ((double)L.E / L.n_pairs)) : 1);
+        TRY(schur_items_build(p, SCHUR_ITEMS_WEIGHTED, &p->items_w, dg_weight));
         HIP_TRY(hipStreamSynchronize(st));
         return 0;
     }();
@@ -1123,7 +972,7 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
             TRY(dev_alloc(p, &p->d_part3, (size_t)p->M * std::max(64, std::max(chunks, chunks_w)) * (cam_acc_len(p->NP) + p->NP)));
         }
         if (p->L.C > 1) TRY(dev_alloc(p, &p->d_pair_part, (size_t)p->L.C * std::max<long long>(p->L.n_pairs, 1) * p->NP * p->NP));
-        TRY(schur_item_table(p));
+        TRY(schur_item_tables(p));
         p->stage_len = std::max<size_t>(std::max<size_t>(n, 2 * (size_t)K), (size_t)6 * p->N) + 16;
         TRY(dev_alloc(p, &p->d_stage, p->stage_len));
         p->xb_len = satba_exchange_len(p);
@@ -1494,7 +1343,7 @@ static int linearize_impl(satba_problem* p, const PhaseCtx& c) {
     if (p->cam_sums_lds) {
         // unit weights + linear loss + affine R+T: the translation entries of diag(U_c) are (observation count) x constants
         // and were not accumulated by the kernel (lin_const_t in satba_kernels.h)
-        const int const_t = lin_const_t(p->model, p->NP, p->loss != 0, p->loss == 0 && p->unit_weights) && lin_variant(p) == 0;
+        const int const_t = lin_const_t(p->model, p->NP, p->loss != 0, unit_run(p)) && lin_variant(p) == 0;
         const int total = p->M * 2 * p->NP;
         hipLaunchKernelGGL(k_lin_finish, dim3((total + 63) / 64), dim3(1024), 0, p->stream, p->M, p->NP, p->lin_grid, p->d_part, U, gc,
                            p->L.cam_ofs, p->d_camc, p->n_cam_fix, const_t, p->d_fx, p->d_fxe, p->d_fxflag, p->d_xb + SATBA_HDR_FX, c.gate);
@@ -1544,265 +1393,8 @@ int satba_prepare(satba_problem* p, int32_t first) {
     return prepare_impl(p, PhaseCtx{}, first);
 }
 
-// automatic: the damping comes from the prepare header and the trust radius Delta (satba_schur_auto), which consumes the prepare header
-static int schur_impl(satba_problem* p, const PhaseCtx& c, FrontCtx f, double lam, bool automatic, double Delta, double lam_floor) {
-    Range range_("satba:schur");
-    if (!p->linearized || (automatic && !p->prepared)) return fail(SATBA_E_STATE, automatic ? "schur_auto before prepare" : "schur before linearize");
-    if (automatic) p->prepared = false;
-    const size_t nS = (size_t)p->n_c * p->n_c + p->n_c;
-    const bool pairs_run = p->L.n_pairs > 0 && p->L.E > 0;
-    const double* lam_dev = automatic ? p->d_keep + SATBA_KEEP_LAM : nullptr;
-    if (p->N > 0) {
-        const bool w = wmode(p) && p->L.wl_ready;  // the records go into the merged records W, behind the row scales k_linearize left there
-        hipLaunchKernelGGL(k_vinv, dim3((p->N + VINV_THREADS - 1) / VINV_THREADS), dim3(VINV_THREADS), 0, p->stream, p->N, lam, automatic ? p->d_xb : nullptr, Delta, lam_floor,
-                           p->d_keep, p->d_V, p->d_scale_inv + p->n_c, p->d_Vinv, p->d_x + p->n_c, p->d_g + p->n_c, w ? reinterpret_cast<double*>(p->d_W) : p->d_PV,
-                           p->L.perm, p->n_pts_fix, automatic ? c.Delta_dev : nullptr, automatic ? c.lam_force_dev : nullptr, c.gate,
-                           w ? p->L.w_fix : (const int*)nullptr);
-    } else if (automatic) {
-        hipLaunchKernelGGL(k_lambda, dim3(1), dim3(1), 0, p->stream, p->d_xb, Delta, lam_floor, p->d_keep, c.Delta_dev, c.lam_force_dev, c.gate);
-    }
-    HIP_TRY(hipGetLastError());
-    // The header is cleared by k_schur_finish (k_vinv reads it).  S and rhs are only cleared when no pair kernel will run: every block
-    // of the lower triangle is otherwise written by the kernels below (k_schur_finish the diagonal blocks and rhs, the pair kernel or
-    // k_schur_finish every off-diagonal block).
-    if (!pairs_run) HIP_TRY(hipMemsetAsync(p->d_xb + p->hdr, 0, sizeof(double) * nS, p->stream));
-    f.lam = lam; f.lam_dev = lam_dev;
-    return launch_schur_kernel(p, c.gate, f);
-}
-
-// schur (+ auto damping) and solve of a front
-// One rank, unit weights, more than two tile columns: the tile factorisation is launched FIRST, on a stream of its own, and works
-// beside the pair kernel -- the rows of the pair triangle are finished in ascending order (schur_item_table), i.e. the columns of S
-// from the left, and every tile of the factorisation waits for the producers of its columns (C3Args::arrive).  The workgroups of
-// the factorisation (SATBA_CHOL_BESIDE_WGS, 1024 threads each: a CU of their own) are resident before the Schur kernels fill the chip.
-static bool chol_beside_ok(const satba_problem* p) {
-    const char* env = getenv("SATBA_CHOL_BESIDE");  // (read at every front: the tests switch it inside one process)
-    if (env && atoi(env) == 0) return false;
-    // unit weights: one item per pair (the table exists from 8 192 pairs on, or SATBA_SCHUR_MERGE); weighted / robust: the chunk items, the
-    // last one of a pair adds the partials (SchurArgs::pair_cnt) -- affine and perspective cameras (the RPC kernel keeps its reduce pass)
-    const bool unit = p->loss == 0 && p->unit_weights;
-    const char* mg = getenv("SATBA_SCHUR_MERGE");
-    const bool enough = p->L.n_pairs >= 8192 || (mg && atoi(mg) != 0);
-    // weighted / robust (round 5): the pair kernel also carries the diagonal blocks and the right-hand side as items of its own, and
-    // their last one per camera adds them up (SchurArgs::dg_cnt)
-    const bool items_ok = unit ? (p->d_item_desc_merged || p->L.C == 1) : (enough && p->model != RPC);
-    return p->world == 1 && items_ok && p->L.n_pairs > 0 && p->L.E > 0 && p->n_c == p->M * p->NP && p->n_c > 128 && p->n_c <= 1024 && p->N > 0 &&
-           !p->beside_off;
-}
-// header slot SATBA_HDR_CHOL_FAIL of the solve phase = lead x status word of the factorisation: SATBA_CHOL_TIMEOUT = a wait timed out.  Beside the pair kernel that
-// means the two kernels did not run at the same time (a profiler collecting counters serialises the launches): the handle goes back
-// to one kernel after the other and the caller repeats the front with the same damping.
-static void beside_disable(satba_problem* p) {
-    // (the interval in force is doubled AFTER it has been used: the first one is 64 sequential fronts, as the field says)
-    if (p->beside_timeouts > 0) p->beside_retry_after = std::min(p->beside_retry_after * 2, 1 << 20);
-    p->beside_off = true; p->beside_clean = 0; ++p->beside_timeouts;
-    (void)hipStreamSynchronize(p->chol_stream);
-    (void)hipMemsetAsync(p->d_arrive, 0, sizeof(int) * (size_t)(p->M + 2) * SCHUR_ARRIVE_STRIDE, p->stream);
-    (void)hipMemsetAsync(p->d_pair_cnt, 0, sizeof(int) * (size_t)std::max<long long>(p->L.n_pairs, 1), p->stream);
-    (void)hipMemsetAsync(p->d_dg_cnt, 0, sizeof(int) * (size_t)p->M, p->stream);
-}
-static bool beside_timed_out(satba_problem* p, const double* h) {
-    if (!p->beside_last || !(h[SATBA_HDR_CHOL_FAIL] >= SATBA_CHOL_BESIDE_WAIT)) return false;  // (a wait between the two kernels)
-    beside_disable(p);
-    return true;
-}
-// ---- the factorisation on a stream of its own, reading every tile of S when its producers have counted in (C3Args::arrive): beside the
-// pair kernel on one rank (front_schur_solve), beside the all-reduce of S cut into messages with several (satba_solve_messages_*)
-static int chol_front_streams(satba_problem* p) {
-    if (p->chol_stream) return 0;
-    // A priority of its own: streams of one priority share a small pool of hardware queues, and two streams on ONE queue run in
-    // submission order -- the factorisation, queued first, would wait for a pair kernel stuck behind it until its waits time out
-    // (seen once in a long test process, where the pool had been handed round many times).
-    int least = 0, greatest = 0, mine = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(hipStreamGetPriority(p->stream, &mine));
-    HIP_TRY(hipStreamCreateWithPriority(&p->chol_stream, hipStreamNonBlocking, mine != greatest ? greatest : least));
-    HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-    TRY(dev_alloc(p, &p->d_arrive, (size_t)(p->M + 2) * SCHUR_ARRIVE_STRIDE));  // (+ k_schur_pairs' start word, + the solve's done word)
-    HIP_TRY(hipMemsetAsync(p->d_arrive, 0, sizeof(int) * (size_t)(p->M + 2) * SCHUR_ARRIVE_STRIDE, p->stream));
-    TRY(dev_alloc(p, &p->d_pair_cnt, (size_t)std::max<long long>(p->L.n_pairs, 1)));
-    HIP_TRY(hipMemsetAsync(p->d_pair_cnt, 0, sizeof(int) * (size_t)std::max<long long>(p->L.n_pairs, 1), p->stream));
-    TRY(dev_alloc(p, &p->d_dg_cnt, (size_t)p->M));
-    HIP_TRY(hipMemsetAsync(p->d_dg_cnt, 0, sizeof(int) * (size_t)p->M, p->stream));
-    return 0;
-}
-// k_chol_tiles (wgs workgroups) and the backward substitution on the other stream, behind everything queued on p->stream so far; *epoch:
-// the launch's epoch (FrontCtx::arrive_epoch, chol_front_finish).  arr_extra: C3Args::arr_extra.
-static int chol_front_launch(satba_problem* p, const int* gate, int wgs, int arr_extra, long long arr_timeout, int* epoch) {
-    Range range_("satba:solve");
-    double* S = p->payload();
-    double* rhs = S + (size_t)p->n_c * p->n_c;
-    const int n = p->n_c;
-    HIP_TRY(hipEventRecord(p->ev_fork, p->stream));
-    HIP_TRY(hipStreamWaitEvent(p->chol_stream, p->ev_fork, 0));
-    HIP_TRY(hipMemsetAsync(p->d_fail, 0, sizeof(int) * (1 + CH_MAX_STEPS), p->chol_stream));
-    cholesky_init();
-    C3Args g;
-    g.A = S; g.n = n; g.b = p->d_dch; g.fail = p->d_fail; g.flags = p->chol.flags; g.epoch = ++p->chol.epoch; g.Linv = p->chol.Linv; g.Cc = p->chol.Cc;
-    g.ctr = p->chol.ctr; g.dinv = p->d_dinv; g.ts = nullptr; g.mirror = 1;
-#ifdef C3_STAMPS
-    if (!p->d_ts) { TRY(dev_alloc(p, &p->d_ts, (size_t)20 * C3_TS)); }
-    HIP_TRY(hipMemsetAsync(p->d_ts, 0, sizeof(long long) * 20 * C3_TS, p->chol_stream));
-    g.ts = p->d_ts;
-#endif
-    g.arrive = p->d_arrive; g.arr_M = p->M; g.np = p->NP; g.arr_epoch = g.epoch; g.si = p->d_scale_inv; g.rhs = rhs;
-    g.arr_extra = arr_extra;
-    g.arr_timeout = arr_timeout;
-    hipLaunchKernelGGL(k_chol_tiles, dim3(std::min(chol_tiles_grid(n, 1), wgs)), dim3(1024), c3_lds_bytes(), p->chol_stream, g, gate);
-    hipLaunchKernelGGL(k_trsv_back_mw, dim3((n + CH_SB - 1) / CH_SB), dim3(512), 0, p->chol_stream, S, p->d_dinv, n, p->d_dch,
-                       p->d_fail + 1 + CH_TRSV_FLAGS, gate, p->d_arrive + (size_t)SCHUR_ARRIVE_STRIDE * (p->M + 1), g.epoch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(p->ev_join, p->chol_stream));
-    *epoch = g.epoch;
-    return 0;
-}
-// the rest of the solve phase on p->stream: k_unscale waits for the word the backward substitution posts on the other stream (the event
-// only orders what follows), then the points' part of the step
-static int chol_front_finish(satba_problem* p, const int* gate, int epoch) {
-    const int nu = std::max(p->n_c, (int)p->hdr);
-    hipLaunchKernelGGL(k_unscale, dim3((nu + 255) / 256), dim3(256), 0, p->stream, p->n_c, p->d_scale_inv, p->d_dch, p->d_dc, (int)p->hdr,
-                       p->d_xb, p->d_fail, p->lead, p->d_keep, SATBA_HDR_KEEP, SATBA_KEEP_LEN, gate,
-                       p->d_arrive + (size_t)SCHUR_ARRIVE_STRIDE * (p->M + 1), epoch);
-    HIP_TRY(hipGetLastError());
-    TRY(launch_backsub_kernel(p, gate));
-    HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_join, 0));
-    p->have_step = true;
-    return 0;
-}
-
 static int solve_impl(satba_problem* p, const PhaseCtx& c);
-static int front_schur_solve(satba_problem* p, const PhaseCtx& c, bool automatic, double lam, double Delta, double lam_floor) {
-    FrontCtx f;
-    if (p->beside_off && ++p->beside_clean > p->beside_retry_after) p->beside_off = false;  // (chol_beside_ok decides whether it applies at all)
-    p->beside_last = chol_beside_ok(p);
-    if (!p->beside_last) {
-        f.scale_in_finish = p->world == 1 && p->n_c > CH_ONE_LAUNCH;  // (the solve follows at once: nobody looks at S in between)
-        if (const int rc = schur_impl(p, c, f, lam, automatic, Delta, lam_floor)) { p->s_scaled = false; return rc; }
-        return solve_impl(p, c);
-    }
-    TRY(chol_front_streams(p));
-    const char* env_wgs = getenv("SATBA_CHOL_BESIDE_WGS");
-    // workgroups (= CUs) lent to the factorisation, a multiple of the eight XCDs.  Measured at 200 cameras x 5 (round 5, LM it/s): beside the
-    // unit-weight pair kernel (0.43 ms) 16: 777, 24: 819, 28: 820, 32: 841, 36: 793, 40: 788, 48: 783, 64: 802; beside the weighted one
-    // (1.3 ms: the factorisation has three times as long, the pair kernel misses every CU longer) 8: 439, 12: 456, 16: 460, 20: 454,
-    // 24: 436, 32: 433 (the sequential front: 433).  Round 6 (faster chain): unit weights -: 865, 24: 846, 32: 865, 40: 809; soft_l1 8: 460, 16: 486, 24: 486
-    const bool weighted_front = wmode(p) && p->L.wl_ready;
-    const int wgs = (env_wgs && atoi(env_wgs) > 0) ? atoi(env_wgs) : (weighted_front ? 16 : 32);
-    // 5 ms + ~10 x what the kernels in front of a tile's last producer take at HBM speed (hit lists and records: ~100 bytes per hit)
-    const long long timeout = 500000 + (long long)((double)p->L.E * 100.0 / 6e12 * 1e8 * 10.0) + (long long)((double)p->K * 200.0 / 6e12 * 1e8 * 10.0);
-    // (the pair kernel of the weighted / robust runs writes the diagonal blocks and the right-hand side, too: launch_schur)
-    TRY(chol_front_launch(p, c.gate, wgs, weighted_front ? 1 : 0, timeout, &f.arrive_epoch));
-    if (const int rc = schur_impl(p, c, f, lam, automatic, Delta, lam_floor)) {
-        HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_join, 0));  // (the other stream's work is bounded by its time-out)
-        return rc;
-    }
-    return chol_front_finish(p, c.gate, f.arrive_epoch);
-}
-
-// ---- several ranks: the all-reduce of S in messages, the factorisation beside it (round 6).  The packed payload
-// [header | rhs | columns of the lower triangle] is cut at camera boundaries into messages of about equal size; the caller all-reduces
-// message m and tells the handle (satba_solve_messages_arrived), which unpacks its columns and counts their cameras in; k_chol_tiles,
-// launched first on the other stream, takes tile column k when the cameras of its 64 columns are in -- the same arrival words, the same
-// scale-as-you-read arithmetic and therefore the same bits as beside the pair kernel on one rank and as the sequential front.
-// bounds: n_messages + 1 camera indices; the packed range of message m is [pk(bounds[m]), pk(bounds[m + 1])) with
-// pk(c) = hdr + n_c + col_ofs(c n_p) for c > 0 and pk(0) = 0 (the first message carries header and right-hand side).
-static int schur_message_cams(const satba_problem* p, std::vector<int>& cam_bounds) {
-    static const int want = getenv("SATBA_PIPELINE_MESSAGES") ? std::max(1, std::min(16, atoi(getenv("SATBA_PIPELINE_MESSAGES")))) : 4;
-    const long long n = p->n_c, np = p->NP;
-    const long long tri = n * (n + 1) / 2;
-    cam_bounds.assign(1, 0);
-    for (int m = 1; m < want; ++m) {
-        // first camera whose columns start at or behind the fraction m / want of the triangle's entries
-        const long long target = tri * m / want;
-        int c = cam_bounds.back();
-        while (c < p->M && (c * np) * n - (c * np) * ((c * np) - 1) / 2 < target) ++c;
-        if (c > cam_bounds.back() && c < p->M) cam_bounds.push_back(c);
-    }
-    cam_bounds.push_back(p->M);
-    return (int)cam_bounds.size() - 1;
-}
-static long long packed_col_ofs(const satba_problem* p, long long col) {  // index of column `col`'s diagonal entry in the packed payload
-    return p->hdr + p->n_c + col * p->n_c - col * (col - 1) / 2;
-}
-static bool solve_messages_ok(const satba_problem* p) {  // (the tile kernel with mirror and multi-workgroup substitution: as chol_beside_ok)
-    return p->n_c == p->M * p->NP && p->n_c > 128 && p->n_c <= 1024;
-}
-int32_t satba_solve_messages(satba_problem* p, int64_t* bounds, int32_t cap) {
-    if (!p) return -1;
-    if (!solve_messages_ok(p)) return 0;  // the caller all-reduces the whole payload and calls satba_solve
-    std::vector<int> cb;
-    const int nm = schur_message_cams(p, cb);
-    if (bounds) {
-        if (cap < nm + 1) return -1;
-        for (int m = 0; m <= nm; ++m) bounds[m] = m == 0 ? 0 : (m == nm ? satba_packed_schur_len(p) : packed_col_ofs(p, (long long)cb[m] * p->NP));
-    }
-    return nm;
-}
-// pack S | rhs | header into `packed` and launch the factorisation, which waits for the messages
-static int solve_messages_begin_impl(satba_problem* p, const int* gate, double* packed, int packed_already) {
-    if (!packed) return fail(SATBA_E_ARG, "null argument");
-    if (!solve_messages_ok(p)) return fail(SATBA_E_ARG, "the reduced system of this handle is solved in one piece (satba_solve)");
-    TRY(chol_front_streams(p));
-    if (!packed_already) hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, packed, 0, 0, p->n_c, gate);
-    HIP_TRY(hipGetLastError());
-    // a message is a collective of the caller's library between host-side calls: the wait is sized for those, not for a kernel (2 s;
-    // SATBA_PIPELINE_TIMEOUT_MS); a time-out is reported like any failed factorisation
-    static const long long ms = getenv("SATBA_PIPELINE_TIMEOUT_MS") ? atoll(getenv("SATBA_PIPELINE_TIMEOUT_MS")) : 2000;
-    static const int wgs = getenv("SATBA_PIPELINE_WGS") ? std::max(8, atoi(getenv("SATBA_PIPELINE_WGS"))) : 64;
-    return chol_front_launch(p, gate, wgs, 0, ms * 100000, &p->msg_epoch);  // (no Schur kernel of this rank is a producer: no FrontCtx)
-}
-int satba_solve_messages_begin(satba_problem* p, double* packed, int32_t packed_already) {
-    if (!p) return fail(SATBA_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    return solve_messages_begin_impl(p, nullptr, packed, packed_already);
-}
-// message m has been all-reduced in `packed`: its columns into S (message 0: header and right-hand side, too), its cameras counted in
-static int solve_messages_arrived_impl(satba_problem* p, const int* gate, const double* packed, int m) {
-    if (!packed) return fail(SATBA_E_ARG, "null argument");
-    std::vector<int> cb;
-    const int nm = schur_message_cams(p, cb);
-    if (m < 0 || m >= nm || !p->msg_epoch) return fail(SATBA_E_STATE, "no such message, or no satba_solve_messages_begin");
-    const int c_lo = cb[m] * p->NP, c_hi = cb[m + 1] * p->NP;
-    hipLaunchKernelGGL(k_pack_lower, dim3(p->n_c + 1), dim3(256), 0, p->stream, p->n_c, (int)p->hdr, p->d_xb, const_cast<double*>(packed), 1, c_lo, c_hi, gate);
-    hipLaunchKernelGGL(k_mark_arrived, dim3((cb[m + 1] - cb[m] + 63) / 64), dim3(64), 0, p->stream, p->d_arrive, cb[m], cb[m + 1], p->M, p->msg_epoch, m == 0 ? 1 : 0,
-                       gate);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-int satba_solve_messages_arrived(satba_problem* p, const double* packed, int32_t m) {
-    if (!p) return fail(SATBA_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
-    return solve_messages_arrived_impl(p, nullptr, packed, m);
-}
-// the packed payload the device-resident loop's parts 10 - 12 work on (satba_lm_part has no pointer argument)
-int satba_solve_messages_bind(satba_problem* p, double* packed) {
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    p->msg_packed = packed;
-    return 0;
-}
-static int solve_messages_end_impl(satba_problem* p, const int* gate) {
-    if (!p->msg_epoch) return fail(SATBA_E_STATE, "satba_solve_messages_end before _begin");
-    const int epoch = p->msg_epoch;
-    p->msg_epoch = 0;
-    return chol_front_finish(p, gate, epoch);
-}
-int satba_solve_messages_end(satba_problem* p) {
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(p->device));
-    return solve_messages_end_impl(p, nullptr);
-}
-
-int satba_schur(satba_problem* p, double lam) {
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(p->device));
-    return schur_impl(p, PhaseCtx{}, FrontCtx{}, lam, false, 0.0, 0.0);
-}
-int satba_schur_auto(satba_problem* p, double Delta, double lam_floor) {
-    if (!p) return fail(SATBA_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(p->device));
-    return schur_impl(p, PhaseCtx{}, FrontCtx{}, 0.0, true, Delta, lam_floor);
-}
+#include "satba_schur_api.inc"
 
 static int solve_impl(satba_problem* p, const PhaseCtx& c) {
     Range range_("satba:solve");
@@ -2096,7 +1688,7 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
         switch (phase) {
             case 0: return launch_residual(p, false, p->d_f, p->d_scal);
             case 1: return launch_linearize_kernel(p, PhaseCtx{});
-            case 2: return launch_schur_kernel(p, nullptr, FrontCtx{});
+            case 2: return launch_schur_kernel(p, nullptr, FrontCtx{}, schur_route(p, FrontCtx{}));
             case 3: {
                 // factorising an already factorised matrix is meaningless numerically but identical in work
                 return dense_solve(p, nullptr, p->payload(), p->d_dch);

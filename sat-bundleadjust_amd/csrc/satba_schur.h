@@ -327,7 +327,7 @@ __device__ __forceinline__ void schur_diag_walk(const ObsArgs& a, const double2*
                                                 double2* my, double (&acc)[cam_acc_len(NP)]);
 
 // 1-D grid, 4 waves per workgroup, one (pair, chunk) item each, taken from an item table in DISPATCH order that is built
-// for the chip's topology (satba_capi.hip: schur_item_table): workgroup b runs on XCD b % 8 (observed placement; only speed
+// for the chip's topology (satba_schur_items.h: schur_item_order): workgroup b runs on XCD b % 8 (observed placement; only speed
 // depends on it), and every XCD works through the pairs (i, j) of ONE camera i and ONE point-range chunk at a time.  All those
 // items gather from the records of camera i's points in that chunk (~1.6 MB at 200 x 1M x 10M), each record is needed by ~9
 // of them, and the 4 MB L2 of the XCD keeps it: round 1 dispatched chunk-major over all pairs and every XCD streamed the
