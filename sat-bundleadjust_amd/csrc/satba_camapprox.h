@@ -287,9 +287,11 @@ __global__ __launch_bounds__(CAM_THREADS) void k_cam_resect(const CamResectArgs 
 }
 
 // ---- the longitude, correctly rounded.  One ulp of a longitude in degrees (73 deg: 1.4e-14 deg, 1.6e-9 m on the ground) moves the
-// column of the shipped sensors by 2.2e-9 px; the device's atan2 is good to an ulp or two, a host libm rounds correctly.  The
+// column of the shipped sensors by 2.2e-9 px; the device's atan2 is good to an ulp or two, and a host libm's float64 atan2 is
+// not correctly rounded either (numpy.arctan2 missed the rounded value on 227 of 35 010 arguments, tests/test_atan2_host.py).  The
 // value q of the affine expansion is the one quantity compared at the 1e-9 px level, so k_cam_affine takes atan2(y, x) in
-// double-double arithmetic (error-free sums and fma products, ~1e-30 relative) and rounds it once.
+// double-double arithmetic (error-free sums and fma products, ~1e-30 relative) and rounds it once: bit for bit the rounded value of
+// a 200-bit evaluation on those arguments, in all four quadrants and across every seam of the three branches below.
 struct CamDD { double hi, lo; };
 __host__ __device__ inline CamDD cam_dd_norm(double a, double b) {  // |a| >= |b|
 #pragma clang fp contract(off)
@@ -369,8 +371,18 @@ __global__ __launch_bounds__(CAM_THREADS) void k_cam_affine(int n_cam, const dou
     double q[2], D[2][3], geo[3], G[3][3];
     rpc_project<true>(tab, p[0], p[1], p[2], q[0], q[1], D);  // J: the chain of the two analytic Jacobians
     geodetic<false>(p[0], p[1], p[2], geo, G);                // q: the same projection at the correctly rounded longitude
-    geo[1] = cam_atan2_rounded(p[1], p[0]) * (180.0 / M_PI);
-    const double L = (geo[1] - tab[80]) / tab[81], La = (geo[0] - tab[82]) / tab[83], H = (geo[2] - tab[84]) / tab[85];
+    double L;
+    {
+        // The longitude in degrees is ROUNDED before the offset is taken off, as a float64 evaluation of the reference's formula
+        // rounds it.  Contracted into fma(rad, 180 / pi, -offset) the product keeps its extra bits, q then carries the rounding of
+        // the radians only and sits up to half an ulp of the longitude (1.1e-9 px at 107 deg, 2.2e-9 px at 163 deg) from the
+        // float64 value it is compared with: below 1e-9 px at the four shipped points by luck, beyond it in five of the eight
+        // octant placements (tests/test_gpu_octants.py).
+#pragma clang fp contract(off)
+        geo[1] = cam_atan2_rounded(p[1], p[0]) * (180.0 / M_PI);
+        L = (geo[1] - tab[80]) / tab[81];
+    }
+    const double La = (geo[0] - tab[82]) / tab[83], H = (geo[2] - tab[84]) / tab[85];
     double* o = P + (size_t)cam * 12;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {

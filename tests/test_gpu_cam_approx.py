@@ -139,10 +139,11 @@ def expansion_value_error(r, p, col0, row0, q):
 
 @pytest.mark.parametrize("f", [0, 1])
 def test_affine_reproduces_the_expansion_value(gpu, f):
-    """P (p, 1) == q - (col0, row0) to 1e-9 px, q the oracle's float64 projection at p (measured: 4.8e-10, 4.8e-10, 4.6e-10,
-    7.4e-10 px at the four points).
+    """P (p, 1) == q - (col0, row0) to 1e-9 px, q the oracle's float64 projection at p (measured: 3.1e-10, 4.2e-10, 4.7e-10,
+    1.9e-10 px at the four points; in the other octants tests/test_gpu_octants.py).
 
-    This holds only because k_cam_affine takes the longitude correctly rounded (cam_atan2_rounded): one ulp of a longitude of 73 deg
+    This holds only because k_cam_affine takes the longitude correctly rounded (cam_atan2_rounded) and rounds it in degrees before
+    the offset is taken off, as a float64 evaluation does: one ulp of a longitude of 73 deg
     is 1.6e-9 m on the ground and 2.2e-9 px in the column, and with the device's own atan2 the second point of rpc 0 was one ulp
     off (1.38e-9 px).  The other roundings of a float64 evaluation are worth 2 - 4e-10 px each (one ulp of the latitude or of the
     altitude's 6.4e6 m terms), so the oracle's own q sits 0.5 - 1.2e-9 px from the extended-precision value; the second assertion
