@@ -66,7 +66,7 @@ enum {
  * same values, is satba/trf.py's; tests/test_host_logic.py holds the two together). */
 /* left by satba_linearize (rank r also leaves |g_p|_inf of its shard in slot SATBA_HDR_FIXED + r): */
 #define SATBA_HDR_COST 0
-#define SATBA_HDR_FX 5      /* a term of the fixed-point camera sums exceeded its bound (summed over ranks) */
+#define SATBA_HDR_FX 5      /* a term of the fixed-point camera sums exceeded its bound, or a free camera's diag U_c terms all lie below their unit (summed over ranks) */
 #define SATBA_HDR_PREP_GH 6 /* point sums of |g_h|^2, |x_h|^2 when the linearisation did the point part of the prepare phase */
 #define SATBA_HDR_PREP_XS 7
 /* left by satba_prepare: |g_h|^2, |J_h g_h|^2, |x_h|^2, lead * |g_c|_inf */
@@ -484,7 +484,9 @@ int satba_get_layout(satba_problem *p, int32_t which, int64_t n, void *host_out)
  * device-resident loop (n >= 17), [17] the last Schur + solve front had the factorisation running beside the pair
  * kernel (1), not (0), or that mode is switched off on this handle after a wait timed out (-1; it is tried again
  * after 128, 256, ... sequential fronts) (n >= 18), [18] such time-outs so far (n >= 19), [19] diagonal items per (camera,
- * chunk) of the weighted / robust pair kernel, 0 before the merged records exist (n >= 20)                               */
+ * chunk) of the weighted / robust pair kernel, 0 before the merged records exist (n >= 20), [20] log2 of the lanes per point
+ * that the next launch of the point kernels uses with the loss configured now (n >= 21), [21] log2 of the replicas of
+ * k_linearize's camera-sum table in LDS (n >= 22)                                                                        */
 int satba_get_info(const satba_problem *p, double *out, int32_t n);
 /* normal-equation blocks of the last linearize: U (M n_p n_p), g_c (M n_p) as written to the exchange
  * payload, V (N x 6: xx xy xz yy yz zz), g_p (N x 3), points in the caller's order. Any pointer may be NULL.

@@ -96,6 +96,7 @@ struct satba_problem {
     int cam_sums_lds = 1;           // k_linearize accumulates diag U_c / g_c with LDS atomics (0: camera-major pass k_cam_sums)
     int lin_rep_shift = 0;          // log2 of the replicas of that LDS table (few cameras: same-address atomics serialise)
     int deterministic = 0;
+    int split_env = -1;             // SATBA_SPLIT at satba_problem_create (experiments, tests): log2 of the lanes per point, -1 unset (slice_split)
     // fixed-point camera sums of k_linearize (satba_kernels.h): scales / bounds / inverse scales per slot, overflow flag, bounding
     // box of the points at the last satba_set_x, largest weight, most observations of one camera, and the cost of this shard at x
     // (linear loss: bound of a residual) with its copy for the trial point
@@ -324,8 +325,7 @@ static int zero_header(satba_problem* p) {
 // would run its slices alone at the end), every wave walking several slices (for_each_slice balances short and long tracks)
 // log2 of the lanes per point of the slice kernels (SliceUnit): as many as it takes to give the chip ~8 waves per SIMD
 static int slice_split(const satba_problem* p) {
-    static const int env = getenv("SATBA_SPLIT") ? atoi(getenv("SATBA_SPLIT")) : -1;  // experiments: log2
-    if (env >= 0) return std::min(env, 3);
+    if (p->split_env >= 0) return std::min(p->split_env, 3);  // SATBA_SPLIT, read when the handle was created
     if (p->deterministic) return 0;  // the repeatability option keeps the summation order of the plain walk (goldens were made with it)
     int sh = 0;
     while (sh < 3 && ((long long)p->L.n_slices << sh) < 3000) ++sh;  // measured: 2 lanes per point at 100 k points, 8 at 5 k
@@ -873,6 +873,7 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
     p->hdr = SATBA_HDR_FIXED + p->world + (p->world & 1);
     p->lead = p->rank == 0 ? 1.0 : 0.0;
     p->deterministic = ((d->flags & SATBA_FLAG_DETERMINISTIC) || getenv("SATBA_DETERMINISTIC")) ? 1 : 0;
+    if (const char* ss = getenv("SATBA_SPLIT")) p->split_env = atoi(ss);  // experiments, tests (negative: the rule, as unset)
 
     int rc = [&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
@@ -1671,6 +1672,8 @@ int satba_get_info(const satba_problem* p, double* out, int32_t n) {
     if (n > 17) out[17] = p->beside_off ? -1.0 : (p->beside_last ? 1.0 : 0.0);
     if (n > 18) out[18] = p->beside_timeouts;
     if (n > 19) out[19] = p->L.wl_ready ? p->L.dg_spc : 0;
+    if (n > 20) out[20] = slice_split(p);
+    if (n > 21) out[21] = p->lin_rep_shift;
     return 0;
 }
 

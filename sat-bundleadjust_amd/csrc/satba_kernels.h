@@ -761,7 +761,8 @@ __global__ __launch_bounds__(LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6
 // sum the per-workgroup camera partials (diag U_c | g_c per camera; 64-bit fixed point, so any order gives the same bits), take
 // off the n_obs(camera) copies of the conversion constant, scale back and expand to the exchange payload: U (M x NP x NP,
 // diagonal only, rest zero), g_c (M x NP).  64 outputs per workgroup, 16 waves each summing a strided subset of the
-// workgroups.  hdr_flag (the linearize header's FX slot) receives 1 when a term of this shard left its range.
+// workgroups.  hdr_flag (the linearize header's FX slot) receives 1 when a term of this shard left its range, or when the diag U_c
+// terms of a free camera all lie below the unit of their scale (below).
 __global__ __launch_bounds__(1024) void k_lin_finish(int M, int NP, int nblocks, const double* __restrict__ part, double* __restrict__ U,
                                                      double* __restrict__ gc, const int* __restrict__ cam_ofs,
                                                      const double* __restrict__ camc, int n_cam_fix, int const_t,
@@ -803,6 +804,12 @@ __global__ __launch_bounds__(1024) void k_lin_finish(int M, int NP, int nblocks,
         const double fxx = cc[CAMX + 2], fy = cc[CAMX + 3], sk = cc[CAMX + 4];
         const double cnt = cam >= n_cam_fix ? (double)(cam_ofs[cam + 1] - cam_ofs[cam]) : 0.0;
         v = cnt * (k == 3 ? fxx * fxx : sk * sk + fy * fy);
+    } else if (cam >= n_cam_fix && (long long)(s - n_obs * FX_MAGIC_BITS) < (long long)n_obs) {
+        // The terms of this slot (all >= 0) lie below the unit of its scale: the n_obs roundings of up to half a unit are as large as
+        // the sum, typically all of it -- a free camera whose rows the generic robust losses all clamp to sqrt(eps) of their weight
+        // (huber beyond f_scale: rho' + 2 rho'' z = 0) came out with diag U_c = 0 and an x_scale of 1 where float64 has 1e-7.  Same
+        // answer as for a term above the range: the iteration is void, the caller repeats it with the camera-major sums (float64).
+        *hdr_flag = 1.0;
     }
     U[(size_t)cam * NP * NP + k * NP + k] = v;
 }
