@@ -379,6 +379,35 @@ int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t *pt_ofs, con
                         const double *err, int32_t K, const int32_t *priority, int32_t *tree_of, int64_t *n_selected,
                         int32_t *n_trees, double *weights, int64_t *rank, int32_t device, float *kernel_ms);
 
+/* ---- pairwise SIFT matching, the step in front of the track construction (ft_match.py:76-133 with the brute-force matcher of
+ * 3rdparty/sift/simd/sift4ctypes.cpp:125-195).  Stand-alone: no problem handle; one call covers all pairs.  The entries are
+ * detected by their presence; the version number stays.
+ * features: host, n_cam pointers to n_kp[m] x 132 float32 (col, row, scale, orientation, 128 descriptor values); a row whose col is
+ * NaN is padding: it stays a row and never matches.  utm: host, n_cam pointers to n_kp[m] x 2 float64 (east, north).  An image no
+ * pair names is not read and may be NULL.  Images are uploaded and packed once and reused by every pair that names them.
+ * Per pair (im_i, im_j) of pairs and per side, the keypoints whose utm lies strictly inside the pair's box (min_east, max_east,
+ * min_north, max_north; infinite bounds are fine, NaN is an error) are selected, ascending; a NaN coordinate is outside.  For a
+ * selected keypoint i of im_i over the selected j of im_j, ascending: d = sum (a - b)^2, +inf where the gate
+ * fabs(xx_i - xx_j) < epi_thr fails, xx = (s[1] col + s[0] row) + s[2] in float32 in that order without fused multiply-add, s the
+ * rectifying similarity of the side (linalg.c:108-138, in double from F5 = F[0,2], F[1,2], F[2,0], F[2,1], F[2,2] of the pair,
+ * rounded to float32); F5 = NULL: no gate.  distA = the smallest d, among equals the lowest j; distB = the second smallest counted
+ * with multiplicity.  (i, j) is a match when float32(distA) / float32(distB) (relative != 0) or float32(distA) (relative == 0) is
+ * below float32(thr) * float32(thr): no match without a finite candidate or for 0 / 0, and a single finite candidate always
+ * passes the relative test.  Matches come out pair by pair in the caller's order, i ascending inside a pair; kp_i / kp_j index the
+ * images' rows.  Descriptors that are all integers in [0, 255] run on the int8 matrix cores and give the reference's bits
+ * (d < 2^24 is exact in float32 in any order); anything else takes a float32 vector kernel that accumulates in index order.
+ * counts (host, 4 x int64): matches, selected keypoints summed over pairs and sides, pairs with an empty side, the path that
+ * ran (0 int8, 1 float32).  Argument errors (SATBA_E_ARG): an image index outside [0, n_cam), im_i == im_j, a NaN in a box,
+ * thr <= 0.  kernel_ms (may be NULL): from the pack kernel to the last kernel, from HIP events (uploads outside, two reads of
+ * counters inside).  Test switches, read at call time: SATBA_MATCH_FLOAT=1, SATBA_MATCH_CHUNK=<multiple of 16>. */
+typedef struct satba_matches satba_matches;
+int satba_match_pairs(int32_t n_cam, const int64_t *n_kp, const float *const *features, const double *const *utm, int32_t n_pairs,
+                      const int32_t *pairs, const double *boxes, const double *F5, float thr, float epi_thr, int32_t relative,
+                      satba_matches **out, int64_t *counts, int32_t device, float *kernel_ms);
+/* any output may be NULL: pair_ofs (n_pairs + 1: the rows of pair p are pair_ofs[p] .. pair_ofs[p + 1] - 1), kp_i, kp_j (matches) */
+int satba_matches_fetch(satba_matches *m, int64_t *pair_ofs, int32_t *kp_i, int32_t *kp_j);
+void satba_matches_destroy(satba_matches *m);
+
 /* ---- feature tracks from pairwise matches, the step in front of the triangulation (ft_utils.py:65-182
  * feature_tracks_from_pairwise_matches with its baseline check :38-62 filter_C_using_pairs_to_triangulate, and the fixed-first
  * partition of ft_pipeline.py:175-179).  Stand-alone: no problem handle; no dense matrix is built.  Keypoint k of image m has

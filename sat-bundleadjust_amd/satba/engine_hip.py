@@ -36,6 +36,7 @@ SYMBOLS = [
     "satba_rpc_affine_approx", "satba_rpc_perspective_approx", "satba_camera_resection", "satba_rpc_mesh",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
     "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
+    "satba_match_pairs", "satba_matches_fetch", "satba_matches_destroy",
 ]
 
 FLAG_DETERMINISTIC = 1
@@ -165,6 +166,11 @@ def load_library(path=None):
     lib.satba_ftracks_destroy.argtypes = [C.c_void_p]
     lib.satba_ftracks_destroy.restype = None
     lib.satba_tracks_have_pair.argtypes = [C.c_int32, C.c_int64, _lp, _ip, C.c_int32, _ip, C.POINTER(C.c_uint8), C.c_int32]
+    lib.satba_match_pairs.argtypes = [C.c_int32, _lp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, _ip, _dp, _dp, C.c_float, C.c_float,
+                                      C.c_int32, C.POINTER(C.c_void_p), _lp, C.c_int32, _fp]
+    lib.satba_matches_fetch.argtypes = [C.c_void_p, _lp, _ip, _ip]
+    lib.satba_matches_destroy.argtypes = [C.c_void_p]
+    lib.satba_matches_destroy.restype = None
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -1,0 +1,331 @@
+"""
+Pairwise matching of SIFT keypoints on the device (the names of ref:bundle_adjust/feature_tracks/ft_match.py; DESIGN.md "Pairwise
+matching").
+
+`match_stereo_pairs` returns the reference's M x 4 array (kp_i, kp_j, im_i, im_j), the input of `ft_utils`.  Per pair: the box of the
+footprints' intersection, the device match of the keypoints inside it (csrc/satba_match.h behind `satba_match_pairs`: the rule of
+ref:3rdparty/sift/simd/sift4ctypes.cpp:125-195, bit for bit on integer descriptors), the reference's renaming of matched keypoints,
+and its UTM consistency filter.  All pairs go to the device in one call; there is no CPU fallback: without libsatba_hip.so or
+without a GPU the calls raise.
+
+Renaming.  ref:ft_s2p.s2p_match_SIFT maps a match back to indices by its coordinates (`list.index`), so a keypoint is named by the
+first keypoint with the same (col, row) -- SIFT emits one keypoint per orientation at a location.  `canonical=True` (the default)
+reproduces that with one index map per image (keypoints that share a location share their UTM coordinates, so they are inside a
+box together); `canonical=False` returns the matched rows themselves.
+
+Not reproduced: the RANSAC of the reference (`ransac.find_fundamental_matrix` / `cv2.findFundamentalMat`) is random and in neither
+tree; `geometric_filter`, a callable (pix_i, pix_j, matches_ij) -> boolean mask, takes its place when a caller wants one.  The
+pairwise .npy cache files are not read or written, and only "epipolar_based" and "bruteforce" are matched here.
+"""
+import ctypes as ct
+
+import numpy as np
+
+from . import engine_hip as E
+from . import geo_utils
+from .ba_outliers import get_elbow_value
+from .ft_triangulate import _device
+
+_lp = ct.POINTER(ct.c_int64)
+_fp = ct.POINTER(ct.c_float)
+EPIPOLAR_THR = 20.0  # ref:ft_s2p.py:145
+METHODS = ("epipolar_based", "bruteforce")
+
+
+# ----------------------------------------------------------------------------- convex polygons (in place of shapely)
+
+def _ring(poly):
+    """(n, 2) vertices of a footprint / geojson polygon / ring, the closing vertex dropped, counter-clockwise."""
+    if isinstance(poly, dict):
+        poly = poly["geojson"] if "geojson" in poly else poly
+        poly = poly["coordinates"][0]
+    elif hasattr(poly, "exterior"):
+        poly = np.asarray(poly.exterior.coords)
+    r = np.asarray(poly, dtype=np.float64).reshape(-1, 2)
+    if len(r) > 1 and np.array_equal(r[0], r[-1]):
+        r = r[:-1]
+    return r[::-1] if _signed_area(r) < 0 else r
+
+
+def _signed_area(r):
+    if len(r) < 3:
+        return 0.0
+    x, y = r[:, 0], r[:, 1]
+    return 0.5 * float(np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y))
+
+
+def polygon_area(poly):
+    return abs(_signed_area(_ring(poly)))
+
+
+def clip_convex(subject, clip):
+    """Sutherland-Hodgman: the part of the convex polygon `subject` inside the convex polygon `clip`, (n, 2), n = 0 when disjoint."""
+    out, c = [tuple(p) for p in _ring(subject)], _ring(clip)
+    for k in range(len(c)):
+        a, b = c[k], c[(k + 1) % len(c)]
+        inp, out = out, []
+        if not inp:
+            break
+
+        def side(p):
+            return (b[0] - a[0]) * (p[1] - a[1]) - (b[1] - a[1]) * (p[0] - a[0])
+
+        for m in range(len(inp)):
+            p, q = inp[m], inp[(m + 1) % len(inp)]
+            sp, sq = side(p), side(q)
+            if sp >= 0:
+                out.append(p)
+            if (sp > 0 and sq < 0) or (sp < 0 and sq > 0):
+                t = sp / (sp - sq)
+                out.append((p[0] + t * (q[0] - p[0]), p[1] + t * (q[1] - p[1])))
+    return np.asarray(out, dtype=np.float64).reshape(-1, 2)
+
+
+def footprint_intersection(poly_i, poly_j):
+    """(area, box) of the intersection of two convex polygons; box = (min_east, max_east, min_north, max_north), None when the
+    polygons share no area (disjoint, or touching along an edge or at a vertex)."""
+    r = clip_convex(poly_i, poly_j)
+    area = abs(_signed_area(r))
+    if not area > 0.0:
+        return 0.0, None
+    return area, (r[:, 0].min(), r[:, 0].max(), r[:, 1].min(), r[:, 1].max())
+
+
+def compute_pairs_to_match(init_pairs, footprints, optical_centers, min_overlap=0.1, min_baseline=1 / 4, orbit_alt=500000, verbose=True):
+    """ref:ft_match.py:17-73: pairs whose footprints overlap by more than min_overlap of the first, and of those the pairs with a
+    baseline above min_baseline * orbit_alt; pairs of a camera whose every pair has a short baseline are kept for triangulation."""
+
+    def set_pair(i, j):
+        return (min(i, j), max(i, j))
+
+    pairs_to_match, pairs_to_triangulate = [], []
+    for (i, j) in init_pairs:
+        i, j = int(i), int(j)
+        area, _ = footprint_intersection(footprints[i], footprints[j])
+        if area / polygon_area(footprints[i]) > min_overlap:
+            pairs_to_match.append(set_pair(i, j))
+            baseline = np.linalg.norm(np.asarray(optical_centers[i]) - np.asarray(optical_centers[j]))
+            if baseline / orbit_alt > min_baseline:
+                pairs_to_triangulate.append(set_pair(i, j))
+    in_match = set(int(c) for p in pairs_to_match for c in p)
+    in_tri = set(int(c) for p in pairs_to_triangulate for c in p)
+    cams_bad_baseline = list(in_match - in_tri)
+    pairs_to_triangulate.extend([(i, j) for (i, j) in pairs_to_match if i in cams_bad_baseline or j in cams_bad_baseline])
+    if verbose:
+        print("     {} / {} pairs suitable to match".format(len(pairs_to_match), len(init_pairs)))
+        print("     {} / {} pairs suitable to triangulate".format(len(pairs_to_triangulate), len(init_pairs)))
+        if cams_bad_baseline:
+            print("     WARNING: Found {} cameras with insufficient baseline w.r.t. all neighbor cameras".format(len(cams_bad_baseline)))
+            print("              Concerned cameras are: {}".format(cams_bad_baseline))
+    return pairs_to_match, pairs_to_triangulate
+
+
+# ----------------------------------------------------------------------------- host pieces of the reference
+
+def get_pt_indices_inside_utm_bbx(easts, norths, min_east, max_east, min_north, max_north):
+    """ref:ft_match.py:76-90 (what the device's select kernel computes per pair and side)."""
+    east_ok = (easts > min_east) & (easts < max_east)
+    north_ok = (norths > min_north) & (norths < max_north)
+    return np.where(east_ok & north_ok)[0]
+
+
+def filter_matches_inconsistent_utm_coords(matches_ij, utm_i, utm_j):
+    """ref:ft_match.py:220-247."""
+    all_utm_distances = np.linalg.norm(utm_i[matches_ij[:, 0]] - utm_j[matches_ij[:, 1]], axis=1)
+    utm_thr, success = get_elbow_value(all_utm_distances, max_outliers_percent=20, verbose=False)
+    utm_thr = utm_thr + 5 if success else np.max(all_utm_distances)
+    return matches_ij[all_utm_distances <= utm_thr]
+
+
+def keypoints_to_utm_coords(im_features, im_rpc, im_offset, alt, zone=None):
+    """ref:ft_match.py:190-217 with the localisation on the device; `zone` lets the images of a scene share one UTM zone (the
+    reference takes the zone of each image's first keypoint).  The NaN padding of im_features is kept."""
+    im_features = np.asarray(im_features)
+    n_kp = int(np.sum(~np.isnan(im_features[:, 0])))
+    utm_coords = np.full((im_features.shape[0], 2), np.nan)
+    if n_kp:
+        cols = im_features[:n_kp, 0].astype(np.float64) + im_offset["col0"]
+        rows = im_features[:n_kp, 1].astype(np.float64) + im_offset["row0"]
+        lon, lat = im_rpc.localization(cols, rows, np.full(n_kp, float(alt)))
+        east, north = geo_utils.utm_from_lonlat(lon, lat, zone=zone)
+        utm_coords[:n_kp, 0], utm_coords[:n_kp, 1] = east, north
+    utm_coords[n_kp:] = im_features[n_kp:, :2]
+    return utm_coords
+
+
+def rectifying_similarities(F):
+    """(s1, s2), float32[3] each: the similarities (a, b, q) that rectify the two images of an affine fundamental matrix F
+    (Hartley & Zisserman p. 345), computed in double and rounded once, as ref:3rdparty/sift/simd/linalg.c:108-138 does."""
+    c, d, a, b, e = _f5(F)
+    r, s = np.sqrt(a * a + b * b), np.sqrt(c * c + d * d)
+    z, t = np.sqrt(r / s), 0.5 * e / np.sqrt(r * s)
+    zz = 1 / z
+    return (np.array([z * b / r, z * a / r, t], dtype=np.float32), np.array([zz * -d / s, zz * -c / s, -t], dtype=np.float32))
+
+
+def _f5(F):
+    F = np.asarray(F, dtype=np.float64)
+    if F.shape == (5,):
+        return [np.float64(v) for v in F]
+    if F.shape != (3, 3):
+        raise ValueError("F must be a 3 x 3 fundamental matrix, got shape {}".format(F.shape))
+    return [F[0, 2], F[1, 2], F[2, 0], F[2, 1], F[2, 2]]
+
+
+def canonical_index_map(features):
+    """index of the first keypoint with the same (col, row), per keypoint (what `list.index` finds in ref:ft_s2p.py:166-168)"""
+    xy = np.ascontiguousarray(np.asarray(features)[:, :2], dtype=np.float32) + np.float32(0.0)  # -0.0 == 0.0
+    key = xy.view(np.uint32).astype(np.uint64)
+    key = (key[:, 0] << np.uint64(32)) | key[:, 1]
+    _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+    return first[inv.reshape(-1)]
+
+
+# ----------------------------------------------------------------------------- the device match
+
+def _load(a, dtype, cols):
+    if isinstance(a, (str, bytes)) or hasattr(a, "__fspath__"):
+        a = np.load(a, mmap_mode="r")
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError("expected an array of shape (n, {}), got {}".format(cols, a.shape))
+    return a
+
+
+def match_pairs(pairs, features, utm_coords, boxes, F=None, thr=0.6, epi_thr=EPIPOLAR_THR, relative=True, device=None, return_info=False):
+    """
+    satba_match_pairs (include/satba.h): all pairs in one call.  pairs (n, 2) image indices; features / utm_coords: per image an
+    (n_kp, 132) / (n_kp, 2) array or .npy path (images no pair names are not loaded); boxes (n, 4) = min_east, max_east, min_north,
+    max_north; F: None (no gate) or per pair a 3 x 3 matrix (or its five coefficients).  Returns pair_ofs (n + 1), kp_i, kp_j: the
+    matches of pair p are rows pair_ofs[p] : pair_ofs[p + 1], kp_i ascending.  With return_info also a dict: n_selected,
+    n_empty_pairs, path ("int8" | "float32"), kernel_ms.
+    """
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    n_pairs, n_cam = pairs.shape[0], len(features)
+    if len(utm_coords) != n_cam:
+        raise ValueError("features and utm_coords must list the same images")
+    if n_pairs and (pairs.min() < 0 or pairs.max() >= n_cam):
+        raise ValueError("a pair names an image outside 0..{}".format(n_cam - 1))
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 4))
+    if boxes.shape[0] != n_pairs:
+        raise ValueError("one box per pair")
+    F5 = None
+    if F is not None:
+        if len(F) != n_pairs:
+            raise ValueError("one fundamental matrix per pair")
+        F5 = np.ascontiguousarray(np.array([_f5(f) for f in F], dtype=np.float64).reshape(-1, 5))
+    used = set(int(c) for c in pairs.reshape(-1))
+    feats = [_load(features[c], np.float32, 132) if c in used else None for c in range(n_cam)]
+    utms = [_load(utm_coords[c], np.float64, 2) if c in used else None for c in range(n_cam)]
+    n_kp = np.zeros(n_cam, dtype=np.int64)
+    for c in used:
+        if feats[c].shape[0] != utms[c].shape[0]:
+            raise ValueError("image {}: {} keypoints but {} utm rows".format(c, feats[c].shape[0], utms[c].shape[0]))
+        n_kp[c] = feats[c].shape[0]
+    fptr = (ct.c_void_p * n_cam)(*[a.ctypes.data if a is not None else None for a in feats])
+    uptr = (ct.c_void_p * n_cam)(*[a.ctypes.data if a is not None else None for a in utms])
+    p32 = np.ascontiguousarray(pairs, dtype=np.int32)
+    lib = E.load_library()
+    handle, ms = ct.c_void_p(None), ct.c_float(0.0)
+    counts = np.zeros(4, dtype=np.int64)
+    E._check(lib, lib.satba_match_pairs(n_cam, n_kp.ctypes.data_as(_lp), fptr, uptr, n_pairs, E._ptr(p32, E._ip), E._ptr(boxes),
+                                        E._ptr(F5) if F5 is not None else None, float(thr), float(epi_thr), 1 if relative else 0, ct.byref(handle),
+                                        counts.ctypes.data_as(_lp), _device(device), ct.byref(ms)))
+    try:
+        n = int(counts[0])
+        pair_ofs = np.zeros(n_pairs + 1, dtype=np.int64)
+        kp_i, kp_j = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        E._check(lib, lib.satba_matches_fetch(handle, pair_ofs.ctypes.data_as(_lp), E._ptr(kp_i, E._ip), E._ptr(kp_j, E._ip)))
+    finally:
+        lib.satba_matches_destroy(handle)
+    if return_info:
+        return pair_ofs, kp_i, kp_j, {"n_selected": int(counts[1]), "n_empty_pairs": int(counts[2]), "path": ("int8", "float32")[int(counts[3])],
+                                      "kernel_ms": ms.value}
+    return pair_ofs, kp_i, kp_j
+
+
+def _method(tracks_config):
+    method = tracks_config.get("FT_sift_matching", "epipolar_based")
+    if method not in METHODS:
+        raise ValueError("FT_sift_matching must be one of {}, got {!r}".format(METHODS, method))
+    return method
+
+
+def _after_match(m_ij, feats_i, feats_j, utm_i, utm_j, maps, canonical, geometric_filter):
+    """renaming, the caller's geometric filter, the UTM filter: one pair on the host (a pair has few matches)"""
+    n = [m_ij.shape[0]]
+    if m_ij.shape[0] and canonical:
+        m_ij = np.stack([maps[0][m_ij[:, 0]], maps[1][m_ij[:, 1]]], axis=1)
+    if m_ij.shape[0] and geometric_filter is not None:
+        mask = np.asarray(geometric_filter(np.asarray(feats_i[:, :2]), np.asarray(feats_j[:, :2]), m_ij), dtype=bool).reshape(-1)
+        m_ij = m_ij[mask]
+        n.append(m_ij.shape[0])
+    if m_ij.shape[0]:
+        m_ij = filter_matches_inconsistent_utm_coords(m_ij, utm_i, utm_j)
+    n.append(m_ij.shape[0])
+    return m_ij, n
+
+
+def _polygon_box(utm_polygon):
+    r = _ring(utm_polygon)
+    if len(r) == 0:
+        return None
+    return (r[:, 0].min(), r[:, 0].max(), r[:, 1].min(), r[:, 1].max())
+
+
+def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygon, tracks_config, F=None, canonical=True, geometric_filter=None,
+                                device=None):
+    """ref:ft_match.py:93-187 for one pair.  utm_polygon: a ring (n, 2), a geojson polygon, or an object with .exterior.coords.
+    Returns (matches_ij (M, 2) or None, n): n = [matched, after the UTM filter], or [0, 0, 0] when a side has no keypoint inside."""
+    method = _method(tracks_config)
+    box = _polygon_box(utm_polygon)
+    fi, fj, ui, uj = _load(features_i, np.float32, 132), _load(features_j, np.float32, 132), _load(utm_i, np.float64, 2), _load(utm_j, np.float64, 2)
+    if box is None:
+        return None, [0, 0, 0]
+    Fs = [F] if method == "epipolar_based" else None
+    if method == "epipolar_based" and F is None:
+        raise ValueError("epipolar_based matching needs the fundamental matrix of the pair")
+    ofs, kp_i, kp_j, info = match_pairs([(0, 1)], [fi, fj], [ui, uj], [box], F=Fs, thr=tracks_config.get("FT_rel_thr", 0.6), device=device,
+                                        return_info=True)
+    if info["n_empty_pairs"]:
+        return None, [0, 0, 0]
+    maps = (canonical_index_map(fi), canonical_index_map(fj)) if canonical else None
+    m_ij, n = _after_match(np.stack([kp_i, kp_j], axis=1).astype(np.int64), fi, fj, ui, uj, maps, canonical, geometric_filter)
+    return (m_ij if m_ij.shape[0] else None), n
+
+
+def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_config, F=None, canonical=True, geometric_filter=None,
+                       device=None, return_info=False):
+    """
+    ref:ft_match.py:250-339.  features / utm_coords: per image an array or a .npy path; footprints: per image a dict with a
+    "geojson" polygon in UTM coordinates (convex).  F: per pair a 3 x 3 fundamental matrix ("epipolar_based").  Returns the M x 4
+    int64 array (kp_i, kp_j, im_i, im_j), pairs in the given order; a pair whose footprints share no area gives no rows.
+    """
+    method = _method(tracks_config)
+    pairs = [(int(p[0]), int(p[1])) for p in pairs_to_match]
+    if method == "epipolar_based" and (F is None or len(F) != len(pairs)):
+        raise ValueError("epipolar_based matching needs one fundamental matrix per pair")
+    boxes = [footprint_intersection(footprints[i], footprints[j])[1] for i, j in pairs]
+    live = [k for k, b in enumerate(boxes) if b is not None]
+    out = np.zeros((0, 4), dtype=np.int64)
+    info = {"n_selected": 0, "n_empty_pairs": 0, "path": "int8", "kernel_ms": 0.0}
+    if live:
+        Fs = [F[k] for k in live] if method == "epipolar_based" else None
+        used = set(c for k in live for c in pairs[k])
+        if used and not (0 <= min(used) and max(used) < min(len(features), len(utm_coords))):
+            raise ValueError("a pair names an image outside 0..{}".format(len(features) - 1))
+        feats = [_load(features[c], np.float32, 132) if c in used else None for c in range(len(features))]  # loaded once
+        utms = [_load(utm_coords[c], np.float64, 2) if c in used else None for c in range(len(utm_coords))]
+        ofs, kp_i, kp_j, info = match_pairs([pairs[k] for k in live], feats, utms, [boxes[k] for k in live], F=Fs,
+                                            thr=tracks_config.get("FT_rel_thr", 0.6), device=device, return_info=True)
+        maps = {c: canonical_index_map(feats[c]) for c in used} if canonical else None
+        rows = []
+        for m, k in enumerate(live):
+            i, j = pairs[k]
+            m_ij = np.stack([kp_i[ofs[m]:ofs[m + 1]], kp_j[ofs[m]:ofs[m + 1]]], axis=1).astype(np.int64)
+            m_ij, _ = _after_match(m_ij, feats[i], feats[j], utms[i], utms[j], (maps[i], maps[j]) if canonical else None, canonical, geometric_filter)
+            if m_ij.shape[0]:
+                rows.append(np.concatenate([m_ij, np.tile(np.array([[i, j]], dtype=np.int64), (m_ij.shape[0], 1))], axis=1))
+        if rows:
+            out = np.concatenate(rows, axis=0)
+    return (out, info) if return_info else out
