@@ -121,7 +121,7 @@ struct satba_problem {
     // solver state (point parts in internal point order)
     double *d_x = nullptr, *d_xnew = nullptr, *d_camc = nullptr, *d_camc_new = nullptr;
     double *d_scale_inv = nullptr, *d_g = nullptr, *d_gh = nullptr, *d_gn = nullptr, *d_q1 = nullptr, *d_wv = nullptr;
-    double *d_U = nullptr, *d_gc = nullptr, *d_V = nullptr, *d_Vinv = nullptr, *d_PV = nullptr, *d_dc = nullptr, *d_dch = nullptr;
+    double *d_U = nullptr, *d_gc = nullptr, *d_V = nullptr, *d_PV = nullptr, *d_dc = nullptr, *d_dch = nullptr;
     double2 *d_f = nullptr, *d_ftmp = nullptr;  // residual pairs of the current linearisation / of satba_residuals, ELL order
     bool f_valid = false;                       // d_f holds the residuals of the current linearisation
     bool prof_lin = false;                      // satba_profile_linearize: event pairs around k_linearize
@@ -161,6 +161,7 @@ struct satba_problem {
     int beside_timeouts = 0;
     double* d_scal = nullptr;  // 8 private scalars (costs of satba_residuals, timing sinks)
     double* d_keep = nullptr;  // SATBA_KEEP_LEN scalars of the running iteration that outlive the per-phase headers
+    double* d_lam_used = nullptr;  // the damping of the last k_vinv, however it was chosen: k_backsub inverts V + lam Dp^2 with it again
     bool prepared = false;     // left by the prepare phase, read (and cleared) by satba_schur_auto
     double *d_xb_own = nullptr, *d_xb = nullptr;
     long long xb_len = 0;
@@ -520,11 +521,11 @@ static int launch_backsub_kernel(satba_problem* p, const int* gate) {
         SATBA_DISPATCH(p, if constexpr (MODEL == AFFINE) {
             hipLaunchKernelGGL((k_affine_dir_tab<NP>), dim3(1), dim3(1024), 0, p->stream, a, p->d_dc, (const double*)nullptr, (const double*)nullptr);
             hipLaunchKernelGGL((k_backsub<MODEL, NP, CL, RL, true>), dim3(grid), dim3(BS_THREADS), 0, p->stream, a, p->d_dc, p->d_dch, p->lead,
-                               p->d_Vinv, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb);
+                               p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb);
         });
     } else
     SATBA_DISPATCH(p, hipLaunchKernelGGL((k_backsub<MODEL, NP, CL, RL>), dim3(grid), dim3(BS_THREADS), lds, p->stream, a, p->d_dc, p->d_dch, p->lead,
-                                         p->d_Vinv, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb));
+                                         p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -914,7 +915,7 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
         TRY(dev_alloc(p, &p->d_q1, n)); TRY(dev_alloc(p, &p->d_wv, n));
         TRY(dev_alloc(p, &p->d_camc, (size_t)p->M * CAMC)); TRY(dev_alloc(p, &p->d_camc_new, (size_t)p->M * CAMC));
         TRY(dev_alloc(p, &p->d_U, (size_t)p->M * p->NP * p->NP)); TRY(dev_alloc(p, &p->d_gc, p->n_c));
-        TRY(dev_alloc(p, &p->d_V, (size_t)6 * p->N)); TRY(dev_alloc(p, &p->d_Vinv, (size_t)6 * p->N));
+        TRY(dev_alloc(p, &p->d_V, (size_t)6 * p->N));
         TRY(dev_alloc(p, &p->d_PV, (size_t)PV_STRIDE * (p->N + 1)));  // record N: all zeros, the target of lanes past the end of a pair list
         HIP_TRY(hipMemset(p->d_PV + (size_t)PV_STRIDE * p->N, 0, sizeof(double) * PV_STRIDE));
         TRY(dev_alloc(p, &p->d_dc, p->n_c)); TRY(dev_alloc(p, &p->d_dch, p->n_c));
@@ -945,6 +946,8 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
         HIP_TRY(hipHostGetDevicePointer((void**)&p->h_lm_dev, p->h_lm, 0));
         TRY(dev_alloc(p, &p->d_keep, SATBA_KEEP_LEN));
         HIP_TRY(hipMemset(p->d_keep, 0, sizeof(double) * SATBA_KEEP_LEN));
+        TRY(dev_alloc(p, &p->d_lam_used, 1));
+        HIP_TRY(hipMemset(p->d_lam_used, 0, sizeof(double)));
         TRY(dev_alloc(p, &p->d_red, (size_t)RED_SLOTS * RED_MAX_NV * RED_MAX_GRID));
         TRY(dev_alloc(p, &p->d_red_cnt, RED_SLOTS));
         HIP_TRY(hipMemset(p->d_red_cnt, 0, sizeof(unsigned) * RED_SLOTS));

@@ -1533,18 +1533,34 @@ __global__ __launch_bounds__(1024) void k_prepare_cams(int nU, int n_c, int NP, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ point block inverse
+// o = (V + lam diag(s0, s1, s2)^2)^-1, symmetric 3 x 3 as xx xy xz yy yz zz (v: the six entries of V in that order).  One function for
+// k_vinv (the records of the Schur kernels) and k_backsub (the points' part of the step): the same operations in the same order on the
+// same operands, so the two hold the same bits and the inverse is stored nowhere but in the records.
+__device__ __forceinline__ void point_block_inverse(double v0, double v1, double v2, double v3, double v4, double v5, double lam, double s0,
+                                                    double s1, double s2, double (&o)[6]) {
+    const double a = v0 + lam * s0 * s0, b = v1, c = v2;
+    const double d = v3 + lam * s1 * s1, e = v4, f = v5 + lam * s2 * s2;
+    const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
+    const double idet = 1.0 / (a * c00 + b * c01 + c * c02);
+    o[0] = c00 * idet; o[1] = c01 * idet; o[2] = c02 * idet;
+    o[3] = (a * f - c * c) * idet; o[4] = (b * c - a * e) * idet; o[5] = (a * d - b * b) * idet;
+}
+
 // ------------------------------------------------------------------------------------------------ K5 back-substitution
 // t_p = sum_obs Jp^T (Jc dc[cam]) per point in the lane's registers, then the point part of the Gauss-Newton step in scaled
 // variables, gn_h = scale_inv_p * Vinv (g_p - t), and the Gram matrix of (g_h, gn_h): hdr[SATBA_HDR_GRAM_A .. _C] = a, b, c.  The camera part
 // gn_h[0 .. n_c) = dc_h is copied by workgroup 0.  (Round 1 needed a staging buffer and a second kernel for the per-point sums.)
+// Vinv = (V + lam Dp^2)^-1 is formed here from V (point_block_inverse: 30 operations a point in a kernel bound by its table reads);
+// lam_used: the damping k_vinv inverted the records with, left on the device by it (satba_problem::d_lam_used).
 #ifndef SATBA_BS_THREADS
 #define SATBA_BS_THREADS 512
 #endif
 constexpr int BS_THREADS = SATBA_BS_THREADS;
 template <int MODEL, int NP, bool CL, bool RL, bool DG = false>
 __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double* __restrict__ dc, const double* __restrict__ dch,
-                                                        double lead, const double* __restrict__ Vinv, const double* __restrict__ g,
-                                                        const double* __restrict__ scale_inv, const double* __restrict__ gh,
+                                                        double lead, const double* __restrict__ V, const double* __restrict__ lam_used,
+                                                        const double* __restrict__ g, const double* __restrict__ scale_inv, const double* __restrict__ gh,
                                                         double* __restrict__ gn, RedBuf rb, double* __restrict__ hdr) {
     SATBA_GATE(a.gate);
     extern __shared__ __attribute__((aligned(16))) double s_dyn_bs[];
@@ -1632,8 +1648,11 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
             for (int j = 0; j < 3; ++j) t[j] = slice_point_sum(t[j], su.sh);
         }
         if (has && su.g == 0) {
-            const double* vi = Vinv + 6 * (size_t)q;
             const size_t ib = (size_t)a.n_c + 3 * (size_t)q;
+            const double2* v2 = reinterpret_cast<const double2*>(V + 6 * (size_t)q);
+            const double2 va = v2[0], vb = v2[1], vc = v2[2];
+            double vi[6];
+            point_block_inverse(va.x, va.y, vb.x, vb.y, vc.x, vc.y, *lam_used, scale_inv[ib], scale_inv[ib + 1], scale_inv[ib + 2], vi);
             const double r0 = g[ib] - t[0], r1 = g[ib + 1] - t[1], r2 = g[ib + 2] - t[2];
             const double d[3] = {vi[0] * r0 + vi[1] * r1 + vi[2] * r2, vi[1] * r0 + vi[3] * r1 + vi[4] * r2,
                                  vi[2] * r0 + vi[4] * r1 + vi[5] * r2};

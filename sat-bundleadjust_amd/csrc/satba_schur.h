@@ -52,17 +52,20 @@ __device__ inline double schur_lambda(const double* __restrict__ hdr, double Del
 }
 
 // hdr_auto (optional): the damping comes from the prepare header (schur_lambda, Delta / lam_floor / keep as there) instead of `lam`
-// Stores: a lane's 48-byte Vinv row and 128-byte record are strided over the wave (24 and 64 lines per store instruction: the
-// texture path handles one line per cycle); the wave's 64 rows / records are contiguous in memory, so they are transposed through
-// LDS (row strides 48 and 144 bytes: the 16 lanes of a ds_write_b128 phase fall into disjoint banks) and written as three / eight
-// fully coalesced 16-byte stores per lane.  Workgroups of 256 threads, N need not be a multiple of 64.
+// lam_used: the damping the records were inverted with, whichever way it was chosen (argument, header, forced retry): k_backsub inverts
+// V + lam Dp^2 again with it for the points' part of the step -- the inverse is stored in the records only (rounds 1 - 6 also wrote it
+// to a plain array Vinv[6 N] for k_backsub: 48 MB of 268 at a million points).
+// Stores: a lane's 128-byte record is strided over the wave (64 lines per store instruction: the texture path handles one line per
+// cycle); the wave's 64 records are contiguous in memory, so they are transposed through LDS (row stride 144 bytes: the 16 lanes of a
+// ds_write_b128 phase fall into disjoint banks) and written as eight fully coalesced 16-byte stores per lane.  Workgroups of 256
+// threads, N need not be a multiple of 64.
 #ifndef SATBA_VINV_THREADS
 #define SATBA_VINV_THREADS 256
 #endif
 constexpr int VINV_THREADS = SATBA_VINV_THREADS;
 __global__ __launch_bounds__(VINV_THREADS) void k_vinv(int N, double lam, const double* __restrict__ hdr_auto, double Delta, double lam_floor,
                                                        double* __restrict__ keep, const double* __restrict__ V,
-                                                       const double* __restrict__ scale_inv_p, double* __restrict__ Vinv,
+                                                       const double* __restrict__ scale_inv_p, double* __restrict__ lam_used,
                                                        const double* __restrict__ xp, const double* __restrict__ gp, double* __restrict__ PV,
                                                        const int* __restrict__ perm, int n_pts_fix, const double* __restrict__ Delta_dev,
                                                        const double* __restrict__ lam_force, const int* gate, const int* __restrict__ w_fix = nullptr) {
@@ -73,41 +76,24 @@ __global__ __launch_bounds__(VINV_THREADS) void k_vinv(int N, double lam, const 
         lam = *lam_force;
         if (blockIdx.x == 0 && threadIdx.x == 0) keep[SATBA_KEEP_LAM] = lam;
     }
-    __shared__ double2 s_t[VINV_THREADS / 64][64 * 9];  // per wave: 64 records x 144 bytes (the Vinv rows use the front of it)
+    __shared__ double2 s_t[VINV_THREADS / 64][64 * 9];  // per wave: 64 records x 144 bytes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p0 = (blockIdx.x * (VINV_THREADS / 64) + wave) * 64;  // first point of this wave
     if (p0 >= N) return;
     const int p = min(p0 + lane, N - 1);  // lanes past the end repeat the last point (their stores are dropped below)
     if (hdr_auto) lam = schur_lambda(hdr_auto, Delta, lam_floor, keep, p0 + lane == 0);
+    if (p0 + lane == 0) *lam_used = lam;
     const double2* v2 = reinterpret_cast<const double2*>(V + 6 * (size_t)p);
     const double2 va = v2[0], vb = v2[1], vc = v2[2];
     const double* s = scale_inv_p + 3 * (size_t)p;
-    const double a = va.x + lam * s[0] * s[0], b = va.y, c = vb.x;
-    const double d = vb.y + lam * s[1] * s[1], e = vc.x, f = vc.y + lam * s[2] * s[2];
-    const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
-    const double idet = 1.0 / (a * c00 + b * c01 + c * c02);
-    const double o0 = c00 * idet, o1 = c01 * idet, o2 = c02 * idet;
-    const double o3 = (a * f - c * c) * idet, o4 = (b * c - a * e) * idet, o5 = (a * d - b * b) * idet;
+    double o[6];
+    point_block_inverse(va.x, va.y, vb.x, vb.y, vc.x, vc.y, lam, s[0], s[1], s[2], o);
+    const double o0 = o[0], o1 = o[1], o2 = o[2], o3 = o[3], o4 = o[4], o5 = o[5];
     const double x0 = xp[3 * (size_t)p], x1 = xp[3 * (size_t)p + 1], x2 = xp[3 * (size_t)p + 2];
     const double g0 = gp[3 * (size_t)p], g1 = gp[3 * (size_t)p + 1], g2 = gp[3 * (size_t)p + 2];
     const double mp = (perm[p] >= n_pts_fix) ? 1.0 : 0.0;
     double2* t = s_t[wave];
     const int n_here = min(64, N - p0);  // points of this wave
-    // Vinv rows: 3 pieces per point
-    t[3 * lane] = make_double2(o0, o1); t[3 * lane + 1] = make_double2(o2, o3); t[3 * lane + 2] = make_double2(o4, o5);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    {
-        double2* out = reinterpret_cast<double2*>(Vinv + 6 * (size_t)p0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int g = 64 * k + lane;
-            const double2 v = t[g];
-            if (g < 3 * n_here) out[g] = v;
-        }
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
     // records: 8 pieces per point (6 used), LDS row stride 9 pieces
     static_assert(PV_STRIDE == 16, "records are eight 16-byte pieces");
     double2* row = t + 9 * lane;
@@ -435,7 +421,8 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
             double dacc[CU];
 #pragma unroll
             for (int k = 0; k < CU; ++k) dacc[k] = 0.0;
-            schur_diag_walk<MODEL, NP, 64>(a, s.PV, s.cm_rec, s.cm_sc, 1, s.zero_fix, i, (int)dp->lo, (int)dp->hi, lane,
+            // (a fixed camera's sums are zero, cam_mask: its entries are not walked; the item publishes and counts itself as always)
+            schur_diag_walk<MODEL, NP, 64>(a, s.PV, s.cm_rec, s.cm_sc, 1, s.zero_fix, i, (int)dp->lo, i < a.n_cam_fix ? (int)dp->lo : (int)dp->hi, lane,
                                            reinterpret_cast<double2*>(reinterpret_cast<char*>(s_coop) + wave * (64 * 112)), dacc);
             const double cam_mask = i < a.n_cam_fix ? 0.0 : 1.0;
             if constexpr (CU > 32) {  // intrinsics (NP = 8, 11: 44, 77 sums): passes of 64 totals, one per lane
@@ -639,7 +626,10 @@ __device__ __forceinline__ void schur_pairs_body(const ObsArgs& a, const SchurAr
     };
 
     {
-        const long long lo = dp->lo, hi = dp->hi;
+        // a pair with a fixed camera: its block is zero whatever the hits hold (cam_mask below), so its list is not walked -- the item
+        // still writes the block and counts itself in like every other one (n_cam_fix = 1: the whole longest row of the triangle)
+        const bool cam_fixed = i < a.n_cam_fix || j < a.n_cam_fix;
+        const long long lo = dp->lo, hi = cam_fixed ? lo : dp->hi;
         constexpr bool POS = !UNITW || MODEL == RPC;  // positions (and, weighted / robust, scales) ride along
         constexpr bool SCL = !UNITW && MODEL != RPC;
         // Cooperative record gathers.  A gather instruction costs the texture path one tag lookup per distinct line it touches;
@@ -1049,17 +1039,14 @@ __device__ __forceinline__ void schur_diag_body(const ObsArgs& a, const CamMajor
     }
     const int b = c.cam_ofs[cam], e = c.cam_ofs[cam + 1];
     const long long len = e - b;
-    const int lo = b + (int)(len * chunk / n_chunks), hi = b + (int)(len * (chunk + 1) / n_chunks);
+    const int lo = b + (int)(len * chunk / n_chunks);
+    const int hi = cam < a.n_cam_fix ? lo : b + (int)(len * (chunk + 1) / n_chunks);  // fixed camera (block-uniform): zeros, its list is not walked
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double acc[CU];
 #pragma unroll
     for (int k = 0; k < CU; ++k) acc[k] = 0.0;
     schur_diag_walk<MODEL, NP, LINC_THREADS>(a, s.PV, c.pt, c.io, s.wmode ? 1 : PV_STRIDE / 2, s.wmode ? s.zero_fix : (PV_STRIDE / 2) * a.N, cam, lo, hi,
                                              (int)threadIdx.x, s_coop + wave * (64 * 7), acc);
-    if (cam < a.n_cam_fix) {  // fixed camera (block-uniform)
-#pragma unroll
-        for (int k = 0; k < CU; ++k) acc[k] = 0.0;
-    }
 #pragma unroll
     for (int k = 0; k < CU; ++k) {
         const double t = wave_sum(acc[k]);

@@ -146,7 +146,7 @@ int schur_impl(satba_problem* p, const PhaseCtx& c, FrontCtx f, double lam, bool
     if (p->N > 0) {
         const bool w = r.weighted;  // the records go into the merged records W, behind the row scales k_linearize left there
         hipLaunchKernelGGL(k_vinv, dim3((p->N + VINV_THREADS - 1) / VINV_THREADS), dim3(VINV_THREADS), 0, p->stream, p->N, lam, automatic ? p->d_xb : nullptr, Delta, lam_floor,
-                           p->d_keep, p->d_V, p->d_scale_inv + p->n_c, p->d_Vinv, p->d_x + p->n_c, p->d_g + p->n_c, w ? reinterpret_cast<double*>(p->d_W) : p->d_PV,
+                           p->d_keep, p->d_V, p->d_scale_inv + p->n_c, p->d_lam_used, p->d_x + p->n_c, p->d_g + p->n_c, w ? reinterpret_cast<double*>(p->d_W) : p->d_PV,
                            p->L.perm, p->n_pts_fix, automatic ? c.Delta_dev : nullptr, automatic ? c.lam_force_dev : nullptr, c.gate,
                            w ? p->L.w_fix : (const int*)nullptr);
     } else if (automatic) {
