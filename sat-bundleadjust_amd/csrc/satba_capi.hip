@@ -106,7 +106,9 @@ struct satba_problem {
     bool fxcost_valid = false, fxcost_new_valid = false, fxcost0_valid = false;  // left by the pass that wrote the cost (or satba_accept), read by the next linearisation / snapshot
     double w_max = 1.0, n_max_cam = 1.0, fx_shrink = 1.0;
     int fx_fallbacks = 0;
-    bool scales_by_tail = false;   // left by lm_launch_tail (the pattern ended with k_lm_accept_scales), read by the next lm_launch_tick, cleared by lm_drive
+    bool scales_by_tail = false;  // left by lm_launch_tail (the pattern ended with k_lm_accept_scales), read by the next lm_launch_tick, cleared by lm_drive
+    bool gh_in_readers = false; // left by a linearisation that did NOT store g_h and g_h / scale_inv of the points (points_gh_stored): read by the launchers of their readers
+    bool q1_points_unformed = false; // ... and the point entries of d_q1 = g_h / scale_inv are still not there: set by the prepare behind such a linearisation, cleared by the subspace phase (k_subspace_vec writes all of q1)
     bool prep_fused = false;   // left by a linearisation that did the point part of the prepare phase (PhaseCtx::fuse_prep), read by the prepare that follows
     struct LmDev* d_lm = nullptr;  // device-resident LM loop (satba_lmdev.h)
     struct LmSummary* h_lm = nullptr;  // pinned, mapped: the device posts the progress of the loop here
@@ -387,6 +389,7 @@ static int launch_trial(satba_problem* p, const PhaseCtx& c, double c0, double c
     const size_t lds = table_bytes(p);
     TrialArgs t{p->d_x, v0, v1, p->d_scale_inv, p->d_xnew, c0, c1, p->lead, p->d_xb + SATBA_HDR_STEP_SQ, p->d_xb + SATBA_HDR_X_SQ, p->d_fxcost_new, c.coef_dev};
     if (c.decide2_in_trial) { t.lm_st = p->d_lm; t.lm_sum = p->h_lm_dev; }  // (lm_launch_tail: one rank, device-resident loop)
+    if (v0 == p->d_gh && p->gh_in_readers) t.g_pts = p->d_g;  // the point entries of g_h were not stored (points_gh_stored)
     p->fxcost_new_valid = true;
     double* cost = p->d_xb + SATBA_HDR_COST_NEW;
     if (unit_run(p))
@@ -458,12 +461,23 @@ static int raise_lin_limits(satba_problem* p) {
     return 0;
 }
 
-static int launch_linearize_kernel(satba_problem* p, const PhaseCtx& c) {
+// Whether a linearisation stores g_h and g_h / scale_inv of the points.  Not where it does the point part of the prepare phase itself on the
+// default route (one rank, fixed-point camera sums, k_prepare_cams behind it): 48 MB of stores at 1 M points that every reader can form from
+// g and scale_inv -- k_backsub, the trial's k_residual, k_jvp<PRE>, k_subspace_vec (point_gh, point_ghs in satba_kernels.h).  Several ranks,
+// the phase entry points, more than 1 024 camera unknowns and the camera-major sums keep the arrays.
+static bool points_gh_stored(const satba_problem* p, const PhaseCtx& c) {
+    const char* e = getenv("SATBA_STORE_GH");  // A/B runs and the tests' comparison of the two forms (read per call): 1 stores everywhere
+    const bool off = e && atoi(e) != 0;
+    return off || !(c.fuse_prep >= 0 && p->world == 1 && p->n_c <= 1024 && p->cam_sums_lds);
+}
+
+static int launch_linearize_kernel(satba_problem* p, const PhaseCtx& c, bool store_gh) {
     ObsArgs a = obs_args(p, false, c.gate);
     a.sh = slice_split(p);
     a.rev = slice_rev(0);
     if (c.fuse_prep >= 0) {  // single-rank loops: the point part of the prepare phase rides in this kernel
-        a.prep_scale = p->d_scale_inv; a.prep_gh = p->d_gh; a.prep_ghs = p->d_q1;
+        a.prep_scale = p->d_scale_inv;
+        if (store_gh) { a.prep_gh = p->d_gh; a.prep_ghs = p->d_q1; }
         a.prep_first = c.fuse_prep; a.prep_first_dev = c.first_dev;
     }
     const bool prof = p->prof_lin && p->prof_used + 2 <= 2 * 4096;
@@ -521,11 +535,11 @@ static int launch_backsub_kernel(satba_problem* p, const int* gate) {
         SATBA_DISPATCH(p, if constexpr (MODEL == AFFINE) {
             hipLaunchKernelGGL((k_affine_dir_tab<NP>), dim3(1), dim3(1024), 0, p->stream, a, p->d_dc, (const double*)nullptr, (const double*)nullptr);
             hipLaunchKernelGGL((k_backsub<MODEL, NP, CL, RL, true>), dim3(grid), dim3(BS_THREADS), 0, p->stream, a, p->d_dc, p->d_dch, p->lead,
-                               p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb);
+                               p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb, p->gh_in_readers ? nullptr : p->d_gh);
         });
     } else
     SATBA_DISPATCH(p, hipLaunchKernelGGL((k_backsub<MODEL, NP, CL, RL>), dim3(grid), dim3(BS_THREADS), lds, p->stream, a, p->d_dc, p->d_dch, p->lead,
-                                         p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb));
+                                         p->d_V, p->d_lam_used, p->d_g, p->d_scale_inv, p->d_gh, p->d_gn, p->red(RB_BS), p->d_xb, p->gh_in_readers ? nullptr : p->d_gh));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -537,22 +551,23 @@ static int launch_jvp(satba_problem* p, const int* gate, int nv, const double* q
     a.rev = slice_rev(2);
     const int grid = slice_grid(p, JVP_THREADS / 64, 2, a.sh);
     const RedBuf rb = p->red(RB_JVP);
+    const double* g_pre = (pre && p->gh_in_readers) ? p->d_g : nullptr;  // the point entries of q1 = g_h / scale_inv are formed in the kernel
     if (p->dir_global && (nv == 2 || pre)) {  // (affine) direction tables from global memory, built here
         SATBA_DISPATCH(p, if constexpr (MODEL == AFFINE) {
             hipLaunchKernelGGL((k_affine_dir_tab<NP>), dim3(1), dim3(1024), 0, p->stream, a, q1, nv == 2 ? q2 : nullptr, nv == 2 ? p->d_scale_inv : nullptr);
-            if (nv == 1) hipLaunchKernelGGL((k_jvp<MODEL, NP, 1, CL, RL, true, true>), dim3(grid), dim3(JVP_THREADS), 0, p->stream, a, q1, q2, p->d_scale_inv, rb, out);
-            else hipLaunchKernelGGL((k_jvp<MODEL, NP, 2, CL, RL, false, true>), dim3(grid), dim3(JVP_THREADS), 0, p->stream, a, q1, q2, p->d_scale_inv, rb, out);
+            if (nv == 1) hipLaunchKernelGGL((k_jvp<MODEL, NP, 1, CL, RL, true, true>), dim3(grid), dim3(JVP_THREADS), 0, p->stream, a, q1, q2, p->d_scale_inv, rb, out, g_pre);
+            else hipLaunchKernelGGL((k_jvp<MODEL, NP, 2, CL, RL, false, true>), dim3(grid), dim3(JVP_THREADS), 0, p->stream, a, q1, q2, p->d_scale_inv, rb, out, g_pre);
         });
     } else if (nv == 1 && pre) {
         const size_t lds = p->model == AFFINE ? dir_table_bytes(p) : table_bytes(p);
-        SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jvp<MODEL, NP, 1, CL, RL, true>), dim3(grid), dim3(JVP_THREADS), lds, p->stream, a, q1, q2, p->d_scale_inv, rb, out));
+        SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jvp<MODEL, NP, 1, CL, RL, true>), dim3(grid), dim3(JVP_THREADS), lds, p->stream, a, q1, q2, p->d_scale_inv, rb, out, g_pre));
     } else if (nv == 1) {
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jvp<MODEL, NP, 1, CL, RL, false>), dim3(grid), dim3(JVP_THREADS), table_bytes(p), p->stream, a, q1, q2,
-                                             p->d_scale_inv, rb, out));
+                                             p->d_scale_inv, rb, out, g_pre));
     } else {
         const size_t lds = p->model == AFFINE ? std::max(table_bytes(p), 2 * dir_table_bytes(p)) : table_bytes(p);  // affine: two direction tables
         SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jvp<MODEL, NP, 2, CL, RL, false>), dim3(grid), dim3(JVP_THREADS), lds, p->stream, a, q1, q2,
-                                             p->d_scale_inv, rb, out));
+                                             p->d_scale_inv, rb, out, g_pre));
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1342,7 +1357,8 @@ static int linearize_impl(satba_problem* p, const PhaseCtx& c) {
     } else {
         HIP_TRY(hipMemsetAsync(p->d_xb, 0, sizeof(double) * n_clear, p->stream));
     }
-    TRY(launch_linearize_kernel(p, c));
+    const bool store_gh = points_gh_stored(p, c);  // (decided once per linearisation: the kernel and the readers' launchers must agree)
+    TRY(launch_linearize_kernel(p, c, store_gh));
     double* U = p->payload();
     double* gc = U + nU;
     if (p->cam_sums_lds) {
@@ -1359,6 +1375,8 @@ static int linearize_impl(satba_problem* p, const PhaseCtx& c) {
     p->linearized = true; p->have_step = false;
     p->f_valid = !p->cam_sums_lds && p->model == RPC;
     p->prep_fused = c.fuse_prep >= 0;
+    p->gh_in_readers = !store_gh;
+    p->q1_points_unformed = false;
     return 0;
 }
 int satba_linearize(satba_problem* p) {
@@ -1377,6 +1395,7 @@ static int prepare_impl(satba_problem* p, const PhaseCtx& c, int first) {
                            p->d_xb, p->d_U, p->d_gc, p->d_keep, p->d_x, p->d_g, p->d_scale_inv, p->d_gh, p->d_q1, c.first_dev, c.gate);
         HIP_TRY(hipGetLastError());
         TRY(launch_jvp(p, c.gate, 1, p->d_q1, p->d_q1, p->d_xb + SATBA_HDR_JG_SQ, true));  // d_q1 is free until the subspace phase
+        p->q1_points_unformed = p->gh_in_readers;  // (only the camera entries of q1 = g_h / scale_inv were written: satba_get_vector)
         p->prepared = true;
         return 0;
     }
@@ -1440,8 +1459,10 @@ static int subspace_impl(satba_problem* p, const PhaseCtx& c, double alpha, doub
     if (!p->have_step) return fail(SATBA_E_STATE, "subspace before solve");
     if (!c.gate) TRY(zero_header(p));  // (the device-resident loop reads only the slots this phase writes)
     hipLaunchKernelGGL(k_subspace_vec, dim3(grid_for(p->n, 256, 512)), dim3(256), 0, p->stream, p->n, p->n_c, p->lead, alpha,
-                       inv_norm_g, p->d_gh, p->d_gn, p->d_q1, p->d_wv, p->red(RB_SUB), p->d_xb, c.sub_args_dev, c.gate);
+                       inv_norm_g, p->d_gh, p->d_gn, p->d_q1, p->d_wv, p->red(RB_SUB), p->d_xb, c.sub_args_dev, c.gate,
+                       p->gh_in_readers ? p->d_g : nullptr, p->d_scale_inv);
     HIP_TRY(hipGetLastError());
+    p->q1_points_unformed = false;  // (every entry of q1 is written)
     return 0;
 }
 int satba_subspace(satba_problem* p, double alpha, double inv_norm_g) {
@@ -1603,6 +1624,14 @@ int satba_get_vector(satba_problem* p, int32_t which, double* host_out) {
     const double* src[] = {p->d_g, p->d_scale_inv, p->d_gn, p->d_q1, p->d_wv, p->d_xnew, p->d_gh};
     if (which < 0 || which > 6) return fail(SATBA_E_ARG, "unknown vector id %d", which);
     HIP_TRY(hipSetDevice(p->device));
+    // the loops' linearisation leaves the point entries of g_h -- and of q1 = g_h / scale_inv, until a subspace phase overwrites q1 -- to their readers: formed here
+    const bool fill_gh = which == 6 && p->gh_in_readers, fill_q1 = which == 3 && p->gh_in_readers && p->q1_points_unformed;
+    if (fill_gh || fill_q1) {
+        hipLaunchKernelGGL(k_fill_point_gh, dim3(grid_for(p->n - p->n_c, 256, 1024)), dim3(256), 0, p->stream, (long long)p->n_c, (long long)p->n, p->d_g,
+                           p->d_scale_inv, fill_gh ? p->d_gh : (double*)nullptr, fill_q1 ? p->d_q1 : (double*)nullptr);
+        if (fill_q1) p->q1_points_unformed = false;
+        HIP_TRY(hipGetLastError());
+    }
     return download_permuted(p, src[which], host_out, p->n_c, 3);
 }
 
@@ -1694,7 +1723,7 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
     auto once = [&]() -> int {
         switch (phase) {
             case 0: return launch_residual(p, false, p->d_f, p->d_scal);
-            case 1: return launch_linearize_kernel(p, PhaseCtx{});
+            case 1: return launch_linearize_kernel(p, PhaseCtx{}, true);  // (not fused: the flag is not looked at)
             case 2: return launch_schur_kernel(p, nullptr, FrontCtx{}, schur_route(p, FrontCtx{}));
             case 3: {
                 // factorising an already factorised matrix is meaningless numerically but identical in work

@@ -103,8 +103,8 @@ struct ObsArgs {
     // sums of |g_h|^2 and |x_h|^2) is done in the lane that has just formed the point's blocks -- the vector kernel of the prepare
     // phase then only visits the camera entries (it read V, g, x, scale_inv of 3 N entries again: 43 us at 1 M points).  Null: not fused.
     double* prep_scale;                  // scale_inv (whole vector, indexed like x)
-    double* prep_gh;                     // g_h
-    double* prep_ghs;                    // g_h / scale_inv
+    double* prep_gh;                     // g_h                  (both null: not stored -- the readers form g / scale_inv and (g / scale_inv) / scale_inv
+    double* prep_ghs;                    // g_h / scale_inv       themselves from g and scale_inv, which they read anyway: point_gh below)
     const int* prep_first_dev;           // first linearisation of a solve (device-resident loop), else prep_first
     int prep_first;
 };
@@ -445,6 +445,15 @@ constexpr int RES_THREADS = SATBA_RES_THREADS;
 // TRIAL: the kernel forms the trial point itself -- x_new = x + (c0 v0 + c1 v1) / scale_inv for the points (the camera entries and
 // the camera constants at x_new come from k_trial_cams, launched in front) -- and returns |step|^2 and |x|^2 beside the cost: a
 // separate vector kernel moved 120 MB for this at 1 M points (27 us) and cost a launch.  a.x is not read then.
+// g_h and g_h / scale_inv of a point entry where k_linearize did not store them (ObsArgs::prep_gh null): the two divisions of the prepare
+// phase, in its order, on its operands -- g as k_linearize stored it, scale_inv as it left it.  IEEE division, correctly rounded
+// (v_div_scale / v_rcp / v_fma refinement / v_div_fmas / v_div_fixup in every reader's ISA): the same bits as the stored values.
+__device__ inline double point_gh(const double* __restrict__ g, const double* __restrict__ scale_inv, size_t i) { return g[i] / scale_inv[i]; }
+__device__ inline double point_ghs(const double* __restrict__ g, const double* __restrict__ scale_inv, size_t i) {
+    const double si = scale_inv[i];
+    return (g[i] / si) / si;
+}
+
 struct TrialArgs {
     const double* __restrict__ x;          // current variables
     const double* __restrict__ v0;         // two direction vectors in scaled variables ...
@@ -461,6 +470,7 @@ struct TrialArgs {
     // gated off takes it in workgroup 0.  One dependent launch less per tick (4.7 - 5.9 us; 4 % of a 10 x 5 k x 30 k iteration).
     struct LmDev* lm_st = nullptr;
     struct LmSummary* lm_sum = nullptr;
+    const double* __restrict__ g_pts = nullptr;  // not null: v0 is g_h and its POINT entries are formed from g (this pointer) and scale_inv (point_gh)
 };
 __device__ void lm_decide2_body(struct LmDev* gst, double cost_new, double step_sq, double x_sq, struct LmSummary* sum);  // satba_lmdev.h
 template <int MODEL, int NP, bool CL, bool RL, bool UNITW = false, bool TRIAL = false>
@@ -496,7 +506,8 @@ __global__ __launch_bounds__(RES_THREADS) void k_residual(ObsArgs a, double2* __
                 double xn[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const double step = (t.c0 * t.v0[ip + k] + t.c1 * t.v1[ip + k]) / t.scale_inv[ip + k], xi = t.x[ip + k];
+                    const double v0k = t.g_pts ? point_gh(t.g_pts, t.scale_inv, ip + k) : t.v0[ip + k];
+                    const double step = (t.c0 * v0k + t.c1 * t.v1[ip + k]) / t.scale_inv[ip + k], xi = t.x[ip + k];
                     xn[k] = xi + step;
                     if (su.g == 0) { t.x_new[ip + k] = xn[k]; ss += step * step; xx += xi * xi; }
                 }
@@ -726,8 +737,10 @@ __global__ __launch_bounds__(LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6
                     else si = fmax(si, a.prep_scale[ib + k]);
                     a.prep_scale[ib + k] = si;
                     const double h = v[6 + k] / si;
-                    a.prep_gh[ib + k] = h;
-                    a.prep_ghs[ib + k] = h / si;
+                    if (a.prep_gh) {
+                        a.prep_gh[ib + k] = h;
+                        a.prep_ghs[ib + k] = h / si;
+                    }
                     s_gh += h * h;
                     const double xs = xv[k] * si;
                     s_xs += xs * xs;
@@ -1205,11 +1218,13 @@ __global__ __launch_bounds__(1024) void k_affine_dir_tab(ObsArgs a, const double
 
 // For NV vectors given in scaled variables (v = q / scale_inv): sums of (J v_a) . (J v_b) over the observations.
 // NV = 1: out[0] = |J v1|^2.   NV = 2: out[0] = |J v1|^2, out[1] = (J v1).(J v2), out[2] = |J v2|^2.
-// PRE (NV = 1): q1 is already divided by scale_inv (k_prepare_vec)
+// PRE (NV = 1): q1 is already divided by scale_inv (k_prepare_vec).  g_pre (PRE only) not null: the POINT entries of q1 = g_h / scale_inv
+// were not stored and are formed from g_pre = g and scale_inv (point_ghs)
 // DG (affine cameras): the direction tables are read from a.dir_tab (k_affine_dir_tab) instead of being built in the LDS
 template <int MODEL, int NP, int NV, bool CL, bool RL, bool PRE, bool DG = false>
 __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __restrict__ q1, const double* __restrict__ q2,
-                                                     const double* __restrict__ scale_inv, RedBuf rb, double* __restrict__ out) {
+                                                     const double* __restrict__ scale_inv, RedBuf rb, double* __restrict__ out,
+                                                     const double* __restrict__ g_pre) {
     SATBA_GATE(a.gate);
     extern __shared__ __attribute__((aligned(16))) double s_dyn_jvp[];
     const int lane = threadIdx.x & 63;
@@ -1228,7 +1243,8 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
                 const size_t ip = (size_t)a.n_c + 3 * (size_t)q;
                 X = a.x[ip]; Y = a.x[ip + 1]; Z = a.x[ip + 2];
                 const double mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
-                v0 = mp * q1[ip]; v1 = mp * q1[ip + 1]; v2 = mp * q1[ip + 2];
+                if (g_pre) { v0 = mp * point_ghs(g_pre, scale_inv, ip); v1 = mp * point_ghs(g_pre, scale_inv, ip + 1); v2 = mp * point_ghs(g_pre, scale_inv, ip + 2); }
+                else { v0 = mp * q1[ip]; v1 = mp * q1[ip + 1]; v2 = mp * q1[ip + 2]; }
             }
             int pos = su.pos;
             const int io0 = has ? a.ipt_ofs[q] : 0;
@@ -1342,7 +1358,7 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
                 mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    if constexpr (PRE) p1[j] = q1[ip + j];
+                    if constexpr (PRE) p1[j] = g_pre ? point_ghs(g_pre, scale_inv, ip + j) : q1[ip + j];
                     else {
                         const double si = 1.0 / scale_inv[ip + j];
                         p1[j] = q1[ip + j] * si;
@@ -1561,7 +1577,9 @@ template <int MODEL, int NP, bool CL, bool RL, bool DG = false>
 __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double* __restrict__ dc, const double* __restrict__ dch,
                                                         double lead, const double* __restrict__ V, const double* __restrict__ lam_used,
                                                         const double* __restrict__ g, const double* __restrict__ scale_inv, const double* __restrict__ gh,
-                                                        double* __restrict__ gn, RedBuf rb, double* __restrict__ hdr) {
+                                                        double* __restrict__ gn, RedBuf rb, double* __restrict__ hdr, const double* __restrict__ gh_pts) {
+    // gh: its camera entries are read.  gh_pts: g_h of the points (= gh where k_linearize or k_prepare_vec stored them); null: a point's g_h
+    // is formed from g and scale_inv, both read here anyway (point_gh)
     SATBA_GATE(a.gate);
     extern __shared__ __attribute__((aligned(16))) double s_dyn_bs[];
     const int lane = threadIdx.x & 63;
@@ -1658,7 +1676,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
                                  vi[2] * r0 + vi[4] * r1 + vi[5] * r2};
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const double v = d[k] * scale_inv[ib + k], h = gh[ib + k];
+                const double v = d[k] * scale_inv[ib + k], h = gh_pts ? gh_pts[ib + k] : point_gh(g, scale_inv, ib + k);
                 gn[ib + k] = v;
                 sa += h * h; sb += h * v; sc += v * v;
             }
@@ -1674,12 +1692,14 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
 __global__ __launch_bounds__(256) void k_subspace_vec(int n, int n_c, double lead, double alpha, double s,
                                                       const double* __restrict__ gh, const double* __restrict__ gn,
                                                       double* __restrict__ q1, double* __restrict__ wv, RedBuf rb,
-                                                      double* __restrict__ hdr, const double* __restrict__ args_dev, const int* gate) {
+                                                      double* __restrict__ hdr, const double* __restrict__ args_dev, const int* gate,
+                                                      const double* __restrict__ g_pts, const double* __restrict__ scale_inv) {
+    // g_pts not null: the point entries of gh were not stored (point_gh)
     SATBA_GATE(gate);
     if (args_dev) { alpha = args_dev[0]; s = args_dev[1]; }  // device-resident loop
     double ww = 0.0, wq = 0.0, gw = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const double h = gh[i], q = s * h, w = gn[i] - alpha * h;
+        const double h = (g_pts && i >= n_c) ? point_gh(g_pts, scale_inv, (size_t)i) : gh[i], q = s * h, w = gn[i] - alpha * h;
         q1[i] = q;
         wv[i] = w;
         const double wgt = (i < n_c) ? lead : 1.0;
@@ -1691,6 +1711,14 @@ __global__ __launch_bounds__(256) void k_subspace_vec(int n, int n_c, double lea
 }
 
 // ------------------------------------------------------------------------------------------------ inspection
+// the point entries of g_h (gh) and of g_h / scale_inv (ghs; null: not wanted) where k_linearize did not store them (satba_get_vector)
+__global__ __launch_bounds__(256) void k_fill_point_gh(long long n_c, long long n, const double* __restrict__ g, const double* __restrict__ scale_inv,
+                                                       double* __restrict__ gh, double* __restrict__ ghs) {
+    for (long long i = n_c + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (gh) gh[i] = point_gh(g, scale_inv, (size_t)i);
+        if (ghs) ghs[i] = point_ghs(g, scale_inv, (size_t)i);
+    }
+}
 // materialised, weighted, row-scaled Jacobian blocks in the CALLER's observation order (parity tests)
 template <int MODEL, int NP>
 __global__ void k_jacobian(ObsArgs a, const int* __restrict__ pts_ind, const int* __restrict__ rank, const int* __restrict__ obs_pos,
