@@ -515,7 +515,8 @@ int satba_get_layout(satba_problem *p, int32_t which, int64_t n, void *host_out)
  * after 128, 256, ... sequential fronts) (n >= 18), [18] such time-outs so far (n >= 19), [19] diagonal items per (camera,
  * chunk) of the weighted / robust pair kernel, 0 before the merged records exist (n >= 20), [20] log2 of the lanes per point
  * that the next launch of the point kernels uses with the loss configured now (n >= 21), [21] log2 of the replicas of
- * k_linearize's camera-sum table in LDS (n >= 22)                                                                        */
+ * k_linearize's camera-sum table in LDS (n >= 22), [22] the first camera whose diagonal block and right-hand-side entries the
+ * last Schur front produced BEHIND its pair kernel (csrc/satba_diag_split.h; the number of cameras: none; -1: no front yet) (n >= 23) */
 int satba_get_info(const satba_problem *p, double *out, int32_t n);
 /* normal-equation blocks of the last linearize: U (M n_p n_p), g_c (M n_p) as written to the exchange
  * payload, V (N x 6: xx xy xz yy yz zz), g_p (N x 3), points in the caller's order. Any pointer may be NULL.

@@ -34,6 +34,7 @@
 #include "satba_camapprox.h"
 #include "satba_schur.h"
 #include "satba_schur_items.h"
+#include "satba_diag_split.h"
 
 #include <dlfcn.h>
 
@@ -156,6 +157,7 @@ struct satba_problem {
     int msg_epoch = 0;         // != 0 between satba_solve_messages_begin and _end: the epoch its factorisation waits for
     double* msg_packed = nullptr;  // the caller's packed payload of that exchange (device-resident loop: parts 10 - 12)
     bool beside_last = false;  // the last front ran that way
+    int diag_split_last = -1;  // ... with the diagonal pass of the cameras from this one on behind the pair kernel (SchurRoute::c_split; M: none)
     bool beside_off = false;   // ... and timed out waiting for the pair kernel (kernels serialised by a tool, one hardware queue for both streams)
     int beside_clean = 0;      // sequential fronts QUEUED since the time-out (the device-resident loop also queues fronts that pass gated off:
                                // an upper bound of the ones that ran); the concurrent front is tried again after beside_retry_after of
@@ -1707,6 +1709,7 @@ int satba_get_info(const satba_problem* p, double* out, int32_t n) {
     if (n > 19) out[19] = p->L.wl_ready ? p->L.dg_spc : 0;
     if (n > 20) out[20] = slice_split(p);
     if (n > 21) out[21] = p->lin_rep_shift;
+    if (n > 22) out[22] = p->diag_split_last;
     return 0;
 }
 

@@ -157,6 +157,8 @@ struct SchurArgs {
     // it) waits for that count, adds the partials up the way k_schur_finish does (schur_diag_total / schur_diag_store: the same
     // arithmetic in the same order), writes the diagonal block and the camera's entries of the right-hand side and counts the camera
     // in `arrive` -- the factorisation expects M - c counts of camera c then (C3Args::arr_extra) and takes the right-hand side tile by tile
+    // (the same fields serve the LATE part of the unit-weight front's diagonal pass, schur_diag_late_body: there the last chunk workgroup of a
+    // camera to FINISH adds the partials up, and nobody waits)
     int* dg_cnt = nullptr;
     double dg_lam = 0.0, dg_lead = 1.0;
     const double* dg_lam_dev = nullptr;
@@ -1025,18 +1027,12 @@ __device__ __forceinline__ void schur_diag_walk(const ObsArgs& a, const double2*
 // grid (M, chunks): the workgroups of one chunk (the same slice of every camera's point-sorted list, i.e. about the same
 // point range) are dispatched together and share their point records in L2.  part [M][chunks][CU]
 // L: the workgroup's index among the M x n_chunks diagonal workgroups of the launch; s_coop: (LINC_THREADS / 64) x 64 x 7 double2, s_red: the waves' sums
-template <int MODEL, int NP>
-__device__ __forceinline__ void schur_diag_body(const ObsArgs& a, const CamMajor& c, const SchurArgs& s, double* __restrict__ part, const int L, const int M,
-                                                const int n_chunks, double2* s_coop, double (*s_red)[cam_acc_len(NP)]) {
+// schur_diag_chunk: one workgroup, chunk `chunk` of camera `cam`'s list -> the camera's partial number `chunk`.  PUBLISH: the partial is read by
+// another workgroup of the SAME launch (schur_diag_late_body): agent-scope store
+template <int MODEL, int NP, bool PUBLISH>
+__device__ __forceinline__ void schur_diag_chunk(const ObsArgs& a, const CamMajor& c, const SchurArgs& s, double* __restrict__ part, const int cam, const int chunk,
+                                                 const int n_chunks, double2* s_coop, double (*s_red)[cam_acc_len(NP)]) {
     constexpr int CU = cam_acc_len(NP);
-    // s.diag_xcd (chunk count a multiple of 8): workgroup L of the launch runs on XCD L % 8 (observed placement); XCD x takes
-    // the chunks = x (mod 8), every camera's slice of one chunk in a row, so that the records (and, weighted runs, the scale lines)
-    // of a point range are fetched by ONE XCD instead of by the ~6 that hold one of the point's cameras
-    int cam = L % M, chunk = L / M;
-    if (s.diag_xcd) {
-        const int x = L & 7, q = L >> 3;
-        cam = q % M; chunk = (q / M) * 8 + x;
-    }
     const int b = c.cam_ofs[cam], e = c.cam_ofs[cam + 1];
     const long long len = e - b;
     const int lo = b + (int)(len * chunk / n_chunks);
@@ -1056,8 +1052,58 @@ __device__ __forceinline__ void schur_diag_body(const ObsArgs& a, const CamMajor
     if (threadIdx.x < CU) {
         double t = 0.0;
         for (int wv = 0; wv < LINC_THREADS / 64; ++wv) t += s_red[wv][threadIdx.x];
-        part[((size_t)cam * n_chunks + chunk) * CU + threadIdx.x] = t;
+        double* const out = part + ((size_t)cam * n_chunks + chunk) * CU + threadIdx.x;
+        if constexpr (PUBLISH) __hip_atomic_store(out, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *out = t;
     }
+}
+template <int MODEL, int NP>
+__device__ __forceinline__ void schur_diag_body(const ObsArgs& a, const CamMajor& c, const SchurArgs& s, double* __restrict__ part, const int L, const int M,
+                                                const int n_chunks, double2* s_coop, double (*s_red)[cam_acc_len(NP)]) {
+    // s.diag_xcd (chunk count a multiple of 8): workgroup L of the launch runs on XCD L % 8 (observed placement); XCD x takes
+    // the chunks = x (mod 8), every camera's slice of one chunk in a row, so that the records (and, weighted runs, the scale lines)
+    // of a point range are fetched by ONE XCD instead of by the ~6 that hold one of the point's cameras
+    int cam = L % M, chunk = L / M;
+    if (s.diag_xcd) {
+        const int x = L & 7, q = L >> 3;
+        cam = q % M; chunk = (q / M) * 8 + x;
+    }
+    schur_diag_chunk<MODEL, NP, false>(a, c, s, part, cam, chunk, n_chunks, s_coop, s_red);
+}
+// The LATE part of the diagonal pass -- unit-weight front beside the factorisation, cameras [cam0, M) (satba_diag_split.h) -- runs BEHIND the
+// pair items: a launch of its own (k_schur_diag_late) or the trailing workgroups of the pair launch (k_schur_pairs_diag_late).  Workgroup L
+// of it takes chunk L % n_chunks of camera cam0 + L / n_chunks: camera-major, so that low cameras -- the factorisation needs them first --
+// complete first, and with the part starting at a multiple of 8 workgroups XCD x still takes the chunks = x (mod 8) (s.diag_xcd).  Same
+// chunk boundaries and per-chunk sums as schur_diag_body.  The camera's LAST chunk workgroup to finish (s.dg_cnt[cam] counts them, and is
+// left at zero; nobody spins) adds the camera's partials the way k_schur_finish does (schur_diag_total / schur_diag_store: the same
+// arithmetic in the same order), writes the diagonal block and the camera's entries of the right-hand side and counts the camera in
+// `arrive` (C3Args::arr_extra).  A fixed camera publishes zeros and counts itself in like every other one.
+template <int MODEL, int NP>
+__device__ __forceinline__ void schur_diag_late_body(const ObsArgs& a, const CamMajor& c, const SchurArgs& s, double* __restrict__ part, double* __restrict__ S,
+                                                     const int L, const int cam0, const int n_chunks, double2* s_coop, double (*s_red)[cam_acc_len(NP)]) {
+    constexpr int CU = cam_acc_len(NP);
+    const int cam = cam0 + L / n_chunks, chunk = L % n_chunks;
+    schur_diag_chunk<MODEL, NP, true>(a, c, s, part, cam, chunk, n_chunks, s_coop, s_red);
+    __shared__ int s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int old = __hip_atomic_fetch_add(s.dg_cnt + cam, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (old == n_chunks - 1) ? 1 : 0;
+        if (s_last) __hip_atomic_store(s.dg_cnt + cam, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    const double lam = s.dg_lam_dev ? *s.dg_lam_dev : s.dg_lam;
+    for (int o0 = 0; o0 < CU; o0 += LINC_THREADS / 8) {  // eight lanes an output (k_schur_finish's arrangement)
+        const int k = o0 + ((int)threadIdx.x >> 3), sub = (int)threadIdx.x & 7;
+        const bool live = k < CU;
+        const double t = schur_diag_total<true>(part, cam, n_chunks, CU, live ? k : 0, sub, live);
+        if (live && sub == 0) schur_diag_store<true>(cam, k, t, NP, a.n_c, lam, s.dg_lead, s.dg_gc, s.dg_scale_inv, S, s.dg_rhs, nullptr);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(s.arrive + (size_t)SCHUR_ARRIVE_STRIDE * cam, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 template <int MODEL, int NP>
 __global__ __launch_bounds__(LINC_THREADS) void k_schur_diag(ObsArgs a, CamMajor c, SchurArgs s, double* __restrict__ part) {
@@ -1084,6 +1130,30 @@ __global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) void 
     }
     schur_pairs_body<MODEL, NP, UNITW>(a, s, S, blockIdx.x - (unsigned)n_diag_pad, s_coop, s_idx);
 }
+// The late part of the diagonal pass (schur_diag_late_body), placement (a): a launch of its own behind k_schur_pairs, (M - cam0) x n_chunks workgroups
+template <int MODEL, int NP>
+__global__ __launch_bounds__(LINC_THREADS) void k_schur_diag_late(ObsArgs a, CamMajor c, SchurArgs s, double* __restrict__ part, double* __restrict__ S, int cam0, int n_chunks) {
+    SATBA_GATE(a.gate);
+    __shared__ double2 s_coop[(LINC_THREADS / 64) * 64 * 7];
+    __shared__ double s_red[LINC_THREADS / 64][cam_acc_len(NP)];
+    schur_diag_late_body<MODEL, NP>(a, c, s, part, S, (int)blockIdx.x, cam0, n_chunks, s_coop, s_red);
+}
+// ... placement (b): the trailing workgroups of the (unit-weight) pair launch -- k_schur_both with the diagonal workgroups at the END of the
+// grid: they fill the pair kernel's drain as slots free up, in ascending camera order.  Workgroups [0, n_pair_wgs) are the pair kernel's
+// (their indices keep their XCD), [n_pair_pad, ...) the late diagonal ones (n_pair_pad: n_pair_wgs rounded up to a multiple of 8).
+template <int MODEL, int NP>
+__global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, true) void k_schur_pairs_diag_late(ObsArgs a, CamMajor c, SchurArgs s, double* __restrict__ part,
+                                                                                                   double* __restrict__ S, int n_pair_wgs, int n_pair_pad, int cam0, int n_chunks) {
+    SATBA_GATE(a.gate);
+    __shared__ double2 s_coop[4 * 64 * 7];
+    __shared__ unsigned s_idx[4][3 * 64];
+    __shared__ double s_red[4][cam_acc_len(NP)];
+    if ((int)blockIdx.x < n_pair_pad) {
+        if ((int)blockIdx.x < n_pair_wgs) schur_pairs_body<MODEL, NP, true>(a, s, S, blockIdx.x, s_coop, s_idx);
+        return;
+    }
+    schur_diag_late_body<MODEL, NP>(a, c, s, part, S, (int)blockIdx.x - n_pair_pad, cam0, n_chunks, s_coop, s_red);
+}
 
 // End of the Schur phase, one launch (three in rounds 1-3: k_schur_init in front of the phase, k_schur_pairs_reduce and k_schur_diag_finish
 // behind it -- 9 us of a 140 us iteration at 10 cameras):
@@ -1100,12 +1170,20 @@ __global__ __launch_bounds__(256) SATBA_PAIRS_WAVES_ATTR(MODEL, NP, UNITW) void 
 // rhs_scaled (or null): every entry of S passes through this launch and the dense solve follows at once (one rank): the system goes out in
 // scaled variables -- S / (scale_inv_r scale_inv_c), rhs_scaled = rhs / scale_inv, k_scale_system's arithmetic -- and the solver's
 // status word and flags (n_clear ints at clear) are cleared: that launch is gone, too.
+// cam_hi >= 0: only the cameras [0, cam_hi) -- the others' diagonal blocks and right-hand side come BEHIND the pair kernel (schur_diag_late_body),
+// their partials in `part` are still the previous front's and are not touched; the header is cleared as always.  arrive: the factorisation
+// waits beside this stream and takes the diagonal blocks camera by camera (C3Args::arr_extra) -- every camera of this launch is counted in
+// once.  The count is not ordered behind the camera's stores and need not be: every wait of the factorisation also waits for word M
+// (c3_wait_arrive, lane 0), which the pair kernel posts when this launch is complete.  (Counted behind the stores as a producer inside the
+// pair kernel does it -- agent-scope stores, drain, a counter per camera whose last arriver counts the camera in -- this launch took 10.4
+// instead of 5.3 us, in front of the pair kernel: profiles/diag_late_ab.txt.)
 __global__ __launch_bounds__(256) void k_schur_finish(int M, int NP, int n_c, int n_chunks, const double* __restrict__ part, double lam,
                                                       const double* __restrict__ lam_dev, double lead, const double* __restrict__ gc,
                                                       const double* __restrict__ scale_inv, double* __restrict__ S, double* __restrict__ rhs,
                                                       double* __restrict__ xb, int hdr_len, int nb_diag, int red_chunks,
                                                       const int2* __restrict__ pair_ij, const double* __restrict__ pair_part, const int* gate,
-                                                      double* __restrict__ rhs_scaled = nullptr, int* __restrict__ clear = nullptr, int n_clear = 0) {
+                                                      double* __restrict__ rhs_scaled = nullptr, int* __restrict__ clear = nullptr, int n_clear = 0,
+                                                      int cam_hi = -1, int* __restrict__ arrive = nullptr) {
     SATBA_GATE(gate);
     if ((int)blockIdx.x >= nb_diag) {
         const long long n_pairs = (long long)M * (M - 1) / 2;
@@ -1133,8 +1211,9 @@ __global__ __launch_bounds__(256) void k_schur_finish(int M, int NP, int n_c, in
     const int gid = blockIdx.x * blockDim.x + threadIdx.x, idx = gid >> 3, sub = gid & 7;
     if (gid < hdr_len) xb[gid] = 0.0;
     if (gid < n_clear) clear[gid] = 0;
+    if (arrive && gid < cam_hi) __hip_atomic_fetch_add(arrive + (size_t)SCHUR_ARRIVE_STRIDE * gid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (n_chunks <= 0) return;  // the diagonal blocks and the right-hand side are written by the pair kernel itself (SchurArgs::dg_cnt)
-    const bool live = idx < M * CU;
+    const bool live = idx < (cam_hi >= 0 ? cam_hi : M) * CU;
     const int cam = live ? idx / CU : 0, k = live ? idx % CU : 0;
     const double t = schur_diag_total<false>(part, cam, n_chunks, CU, k, sub, live);
     if (!live || sub != 0) return;

@@ -51,6 +51,12 @@ struct SchurRoute {
     int finish_dchunks, finish_red_chunks, nb_diag;
     bool beside_ok;      // the front: the factorisation may run beside the pair kernel ...
     int wgs, arr_extra;  // ... on that many workgroups (default), C3Args::arr_extra
+    // ... and, unit weights, takes the diagonal blocks and the right-hand side of the cameras [c_split, M) from BEHIND the pair kernel
+    // (satba_diag_split.h; M: nothing late) -- k_schur_diag and k_schur_finish in front keep the cameras [0, c_split).  In force on fronts
+    // with the factorisation waiting (FrontCtx::arrive_epoch) only.  late_tail: the late part as trailing workgroups of the pair launch
+    // (k_schur_pairs_diag_late) instead of a launch of its own (k_schur_diag_late)
+    int c_split;
+    bool late_tail;
 };
 
 SchurRoute schur_route(const satba_problem* p, const FrontCtx& f) {
@@ -81,7 +87,15 @@ SchurRoute schur_route(const satba_problem* p, const FrontCtx& f) {
     // unit-weight pair kernel (0.43 ms) 16: 777, 24: 819, 28: 820, 32: 841, 36: 793, 40: 788, 48: 783, 64: 802; beside the weighted one
     // (1.3 ms: the factorisation has three times as long, the pair kernel misses every CU longer) 8: 439, 12: 456, 16: 460, 20: 454,
     // 24: 436, 32: 433 (the sequential front: 433).  Round 6 (faster chain): unit weights -: 865, 24: 846, 32: 865, 40: 809; soft_l1 8: 460, 16: 486, 24: 486
-    r.wgs = r.weighted ? 16 : 32; r.arr_extra = r.weighted ? 1 : 0;  // (the pair kernel of the weighted / robust runs writes the diagonal blocks and the right-hand side, too)
+    // the split of the diagonal pass (read at every front: the tests switch it inside one process).  SATBA_DIAG_LATE_COLS: late tile
+    // columns (0: the undivided pass); SATBA_DIAG_LATE_FROM: c* directly (tests); SATBA_DIAG_LATE_PLACE: a (own launch) | b (tail of the pair launch)
+    const bool split_applies = r.beside_ok && r.unit && !r.dg_in_pairs && r.red_chunks == 1;
+    const char *lf = getenv("SATBA_DIAG_LATE_FROM"), *lc = getenv("SATBA_DIAG_LATE_COLS"), *lp = getenv("SATBA_DIAG_LATE_PLACE");
+    r.c_split = (lf && *lf) ? diag_split_forced(p->M, atoi(lf), split_applies)
+                            : diag_split_camera(p->M, p->NP, (lc && *lc) ? atoi(lc) : diag_late_cols_default(diag_split_tiles(p->M, p->NP)), split_applies);
+    r.late_tail = (lp && *lp) ? (*lp == 'b' || *lp == 'B') : DIAG_LATE_TAIL_DEFAULT;
+    // (the pair kernel of the weighted / robust runs writes the diagonal blocks and the right-hand side, too; late cameras count themselves in)
+    r.wgs = r.weighted ? 16 : 32; r.arr_extra = (r.weighted || r.c_split < p->M) ? 1 : 0;
     return r;
 }
 
@@ -96,7 +110,7 @@ SchurArgs schur_args(const satba_problem* p, const FrontCtx& f, const SchurRoute
     }
     if (f.arrive_epoch) {
         s.arrive = p->d_arrive; s.arrive_epoch = f.arrive_epoch; s.pair_cnt = p->d_pair_cnt; s.fail = p->d_fail;
-        if (r.dg_in_pairs) {
+        if (r.dg_in_pairs || r.c_split < p->M) {
             s.dg_cnt = p->d_dg_cnt; s.dg_lam = f.lam; s.dg_lam_dev = f.lam_dev; s.dg_lead = p->lead; s.dg_gc = p->d_gc;
             s.dg_scale_inv = p->d_scale_inv; s.dg_rhs = rhs;
         }
@@ -110,15 +124,20 @@ int launch_schur(satba_problem* p, const FrontCtx& f, const SchurRoute& r, const
     if (f.arrive_epoch && r.unit && r.red_chunks > 1) return fail(SATBA_E_STATE, "factorisation beside a unit-weight pair kernel with chunk partials");
     const CamMajor cm = cam_major(p, r.cm_rec);
     const SchurArgs s = schur_args(p, f, r, rhs);
+    // cameras [0, c_split) in front of the pair kernel, [c_split, M) behind it (SchurRoute::c_split)
+    const int c_split = f.arrive_epoch ? r.c_split : p->M;
+    const bool late = c_split < p->M;
+    p->diag_split_last = c_split;
     auto finish = [&]() {
         const long long outs = r.finish_red_chunks > 1 ? p->L.n_pairs * NP * NP : 0;
         hipLaunchKernelGGL(k_schur_finish, dim3((unsigned)(r.nb_diag + (outs + 255) / 256)), dim3(256), 0, p->stream, p->M, NP, p->n_c, r.finish_dchunks, p->d_part3,
                            f.lam, f.lam_dev, p->lead, p->d_gc, p->d_scale_inv, S, rhs, p->d_xb, (int)p->hdr, r.nb_diag, r.finish_red_chunks,
                            p->L.pair_ij, p->d_pair_part, a.gate, r.finish_scale ? p->d_dch : (double*)nullptr, r.finish_scale ? p->d_fail : (int*)nullptr,
-                           r.finish_scale ? 1 + CH_MAX_STEPS : 0);
+                           r.finish_scale ? 1 + CH_MAX_STEPS : 0, late ? c_split : -1, late ? p->d_arrive : (int*)nullptr);
         p->s_scaled = r.finish_scale;
     };
-    if (!r.dg_in_pairs && !r.both) hipLaunchKernelGGL((k_schur_diag<MODEL, NP>), dim3(p->M, r.dchunks), dim3(LINC_THREADS), 0, p->stream, a, cm, s, p->d_part3);
+    if (!r.dg_in_pairs && !r.both && c_split > 0)
+        hipLaunchKernelGGL((k_schur_diag<MODEL, NP>), dim3(c_split, r.dchunks), dim3(LINC_THREADS), 0, p->stream, a, cm, s, p->d_part3);
     if (r.finish_first) finish();
     if (r.pairs_run) {
         const dim3 igrid((unsigned)r.items->n_blocks);
@@ -128,9 +147,17 @@ int launch_schur(satba_problem* p, const FrontCtx& f, const SchurRoute& r, const
             if (r.unit) hipLaunchKernelGGL((k_schur_both<MODEL, NP, true>), bgrid, dim3(256), 0, p->stream, a, cm, s, p->d_part3, S, n_diag, n_diag_pad, p->M, r.dchunks);
             else hipLaunchKernelGGL((k_schur_both<MODEL, NP, false>), bgrid, dim3(256), 0, p->stream, a, cm, s, p->d_part3, S, n_diag, n_diag_pad, p->M, r.dchunks);
         }
+        else if (late && r.late_tail) {
+            const int n_pad = ((int)igrid.x + 7) & ~7;
+            hipLaunchKernelGGL((k_schur_pairs_diag_late<MODEL, NP>), dim3((unsigned)(n_pad + (p->M - c_split) * r.dchunks)), dim3(256), 0, p->stream, a, cm, s, p->d_part3, S,
+                               (int)igrid.x, n_pad, c_split, r.dchunks);
+        }
         else if (r.unit) hipLaunchKernelGGL((k_schur_pairs<MODEL, NP, true>), igrid, dim3(256), 0, p->stream, a, s, S);
         else hipLaunchKernelGGL((k_schur_pairs<MODEL, NP, false>), igrid, dim3(256), 0, p->stream, a, s, S);
         HIP_TRY(hipGetLastError());
+        if (late && !r.late_tail)
+            hipLaunchKernelGGL((k_schur_diag_late<MODEL, NP>), dim3((unsigned)((p->M - c_split) * r.dchunks)), dim3(LINC_THREADS), 0, p->stream, a, cm, s, p->d_part3, S,
+                               c_split, r.dchunks);
     }
     if (!r.finish_first) finish();
     HIP_TRY(hipGetLastError());
@@ -260,7 +287,9 @@ int front_schur_solve(satba_problem* p, const PhaseCtx& c, bool automatic, doubl
     TRY(chol_front_streams(p));
     const char* env_wgs = getenv("SATBA_CHOL_BESIDE_WGS");
     const int wgs = (env_wgs && atoi(env_wgs) > 0) ? atoi(env_wgs) : r.wgs;
-    // 5 ms + ~10 x what the kernels in front of a tile's last producer take at HBM speed (hit lists and records: ~100 bytes per hit)
+    // 5 ms + ~10 x what the kernels in front of a tile's last producer take at HBM speed (hit lists and records: ~100 bytes per hit) -- every
+    // kernel of the front is counted, so the sum also covers a tile whose last producer is the late part of the diagonal pass, behind the pair
+    // kernel (SchurRoute::c_split: the same K entries, cut in two); a wait's clock starts when the wait does
     const long long timeout = 500000 + (long long)((double)p->L.E * 100.0 / 6e12 * 1e8 * 10.0) + (long long)((double)p->K * 200.0 / 6e12 * 1e8 * 10.0);
     TRY(chol_front_launch(p, c.gate, wgs, r.arr_extra, timeout, &f.arrive_epoch));
     if (const int rc = schur_impl(p, c, f, lam, automatic, Delta, lam_floor)) {

@@ -538,11 +538,11 @@ class HipEngine:
         return out
 
     def info(self):
-        v = np.zeros(22)
-        _check(self.lib, self.lib.satba_get_info(self._h, _ptr(v), 22))
+        v = np.zeros(23)
+        _check(self.lib, self.lib.satba_get_info(self._h, _ptr(v), 23))
         keys = ["ms_uploads", "ms_sizes", "ms_ell", "ms_pairs", "ms_create", "ell_len", "pair_entries", "pair_chunks", "unit_weights",
                 "camc_lds", "rpc_lds", "cam_sums_lds", "deterministic", "cm_chunks", "lin_grid", "fx_fallbacks", "device_loop", "chol_beside", "chol_beside_timeouts", "diag_items_per_chunk",
-                "lanes_log2", "lin_rep_shift"]
+                "lanes_log2", "lin_rep_shift", "diag_late_from"]
         return dict(zip(keys, v[: len(keys)]))
 
     def get_blocks(self):

@@ -1,5 +1,7 @@
 """Time line of the Schur / solve phase from a rocprofv3 rocpd database: for every launch of the tile Cholesky, where the kernels of
-the phase start and end relative to k_vinv's start (medians over the launches; microseconds)."""
+the phase start and end relative to k_vinv's start (medians over the launches; microseconds).  A front whose diagonal pass is cut in two
+(csrc/satba_diag_split.h) shows both parts: k_schur_diag in front of the pair kernel and k_schur_diag_late behind it, or the one launch
+k_schur_pairs_diag_late that carries the pair items and the late part."""
 import re
 import sqlite3
 import statistics
@@ -18,8 +20,10 @@ def main(path, out=sys.stdout):
     rows = c.execute("select s.{n}, d.{s}, d.{e} from {d} d join {y} s on d.kernel_id = s.id order by d.{s}".format(
         n=name_col, s=start, e=end, d=disp, y=sym)).fetchall()
     rows = [(re.sub(r"\(.*", "", n), a, b) for n, a, b in rows]
-    names = ["k_vinv", "k_schur_diag<", "k_schur_finish", "k_schur_pairs<", "k_chol_tiles", "k_trsv_back_mw", "k_unscale",
-             "k_backsub"]
+    names = ["k_vinv", "k_schur_diag<", "k_schur_finish", "k_schur_pairs<", "k_schur_pairs_diag_late<", "k_schur_diag_late<", "k_chol_tiles",
+             "k_trsv_back_mw", "k_unscale", "k_backsub"]
+    optional = ("k_unscale", "k_schur_diag<", "k_schur_diag_late<", "k_schur_pairs<", "k_schur_pairs_diag_late<")
+    pair_keys = ("k_schur_pairs<", "k_schur_pairs_diag_late<")  # one of the two carries the pair items
     phases = []
     for idx, (n, a, b) in enumerate(rows):
         if "k_vinv" not in n:
@@ -30,7 +34,9 @@ def main(path, out=sys.stdout):
                 if key in n2 and key not in ph and b2 > a:
                     ph[key] = ((a2 - a) / 1e3, (b2 - a) / 1e3)
         # (the weighted Schur complement has no k_schur_diag launch: its diagonal items run inside the pair kernel)
-        if all(k in ph for k in names if k not in ("k_unscale", "k_schur_diag<")):
+        # (... and a front with every camera late has no k_schur_diag launch in front)
+        if all(k in ph for k in names if k not in optional) and any(k in ph for k in pair_keys):
+            ph["pairs"] = ph.get(pair_keys[0]) or ph[pair_keys[1]]
             phases.append(ph)
     if not phases:
         out.write("no Schur / solve phase with the tile Cholesky in this trace\n")
@@ -42,7 +48,7 @@ def main(path, out=sys.stdout):
         s = statistics.median(p[k][0] for p in phases)
         e = statistics.median(p[k][1] for p in phases)
         out.write("{:<22s} {:>9.1f} {:>9.1f} {:>9.1f}\n".format(k.rstrip("<"), s, e, statistics.median(p[k][1] - p[k][0] for p in phases)))
-    tails = sorted(p["k_chol_tiles"][1] - p["k_schur_pairs<"][1] for p in phases)
+    tails = sorted(p["k_chol_tiles"][1] - p["pairs"][1] for p in phases)
     heads = sorted(p["k_chol_tiles"][0] for p in phases)
     q = lambda v, f: v[min(len(v) - 1, int(f * len(v)))]
     out.write("factorisation end - pair kernel end: min {:.1f} median {:.1f} p90 {:.1f} max {:.1f}\n".format(tails[0], q(tails, 0.5), q(tails, 0.9), tails[-1]))
