@@ -408,6 +408,25 @@ int satba_match_pairs(int32_t n_cam, const int64_t *n_kp, const float *const *fe
 int satba_matches_fetch(satba_matches *m, int64_t *pair_ofs, int32_t *kp_i, int32_t *kp_j);
 void satba_matches_destroy(satba_matches *m);
 
+/* ---- SIFT detection and description of one image, the step in front of the matching (ref:s2p/sift.py keypoints_from_nparray,
+ * i.e. sift() of ref:3rdparty/sift/simd/sift4ctypes.cpp:71-123: "Anatomy of the SIFT method" with delta_min 0.5, sigma_min 0.8,
+ * sigma_in 0.5, 36 orientation bins, 4 x 4 x 8 descriptors, 5 interpolation steps, edge 10, lambda_ori 1.5, lambda_des 6, t 0.8).
+ * image: height rows of width float32 pixels on the host, row_stride floats from one row to the next; nb_scales is the number of
+ * scales per octave.  Rows come out as the reference lists them: by (octave, scale, row, column) of the discrete extremum, then
+ * by orientation bin; a row is (col, row, sigma, theta, 128 integers 0 .. 255).  Two calls on one image return identical bytes.
+ * counts (host, 6 x int64): rows, octaves, discrete extrema above 0.8 thr, survivors of the interpolation, survivors of the
+ * border test (keypoints before their orientations), 1 when a pixel is not finite.  SATBA_E_ARG: a side shorter than 12 pixels,
+ * nb_scales outside [1, 13], nb_octaves < 1, thresh_dog < 0 or NaN, row_stride < width.  SATBA_E_NONFINITE: a non-finite pixel.
+ * keep_planes = 1 keeps the Gaussian planes for satba_sift_fetch_plane (plane `scale` of `octave`, 0 .. nb_scales + 2; plane may
+ * be NULL to ask for the size only); with keep_planes = 0 that call returns SATBA_E_STATE.  kernel_ms (may be NULL): from the
+ * seed kernel to the last kernel, from HIP events (the upload outside, three reads of counters inside). */
+typedef struct satba_sift satba_sift;
+int satba_sift_detect(const float *image, int32_t width, int32_t height, int64_t row_stride, float thresh_dog, int32_t nb_octaves,
+                      int32_t nb_scales, int32_t keep_planes, satba_sift **out, int64_t *counts, int32_t device, float *kernel_ms);
+int satba_sift_fetch(satba_sift *s, float *keypoints /* counts[0] x 132 */);
+int satba_sift_fetch_plane(satba_sift *s, int32_t octave, int32_t scale, float *plane, int32_t *w, int32_t *h);
+void satba_sift_destroy(satba_sift *s);
+
 /* ---- feature tracks from pairwise matches, the step in front of the triangulation (ft_utils.py:65-182
  * feature_tracks_from_pairwise_matches with its baseline check :38-62 filter_C_using_pairs_to_triangulate, and the fixed-first
  * partition of ft_pipeline.py:175-179).  Stand-alone: no problem handle; no dense matrix is built.  Keypoint k of image m has

@@ -30,6 +30,7 @@
 #include "satba_tracks.h"
 #include "satba_ftracks.h"
 #include "satba_match.h"
+#include "satba_sift.h"
 #include "satba_rpcfit.h"
 #include "satba_camapprox.h"
 #include "satba_schur.h"
@@ -1759,5 +1760,6 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_tracks_api.inc"
 #include "satba_ftracks_api.inc"
 #include "satba_match_api.inc"
+#include "satba_sift_api.inc"
 
 }  // extern "C"
