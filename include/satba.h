@@ -266,6 +266,15 @@ int satba_lm_step(satba_problem* p, int32_t first, double Delta, double lam_floo
 int satba_lm_run(satba_problem* p, int64_t n_iterations, int32_t cycle_len, double lam_floor, double* out, int32_t n_out);
 int satba_lm_state(satba_problem* p, double* out, int32_t n);
 
+/* The scalar side of the loop on its own, for tests of the two compilations this library carries of it (csrc/satba_lm.h): n rows
+ * in = a b c g0 g1 Delta (host pointers, float64) of the model min 1/2 p^T [[a b] [b c]] p + g^T p, |p| <= Delta; per row
+ * out = p0 p1 newton Delta_new ratio term -- the trust-region step and its Newton flag, then update_tr_radius and
+ * check_termination fed from that step as the loop feeds them (satba_lm::lm_scalars_row).  device == 0: the host compilation (the
+ * host loop's); device == 1: the device compilation (the decision kernels'), one thread per row on the default stream of the current
+ * device.  No handle.  n == 0 returns 0 without a launch.  SATBA_E_ARG, before the device is touched: device not 0 or 1, n < 0 or
+ * n > 2^24, a null pointer with n > 0. */
+int satba_lm_scalars(int32_t device, int64_t n, const double *in, double *out);
+
 /* ---- one-shot solve: the whole trust-region loop (scipy:optimize/_lsq/trf.py:401-560 as ba_core.py:284-297 configures it,
  * with the exact damped step of this library) below the ABI, for callers that do not want to drive the phases themselves.
  * Starts from the current x (satba_set_x), leaves the solution in the handle (satba_get_x, satba_residuals).  Single-rank

@@ -516,3 +516,38 @@ int satba_solve_lm(satba_problem* p, const satba_lm_opts* o, satba_lm_stats* out
     }
     return 0;
 }
+
+// satba_lm_scalars (include/satba.h): stand-alone (no handle).  The scalar functions of satba_lm.h as this library carries them, once per
+// row: device == 0 the host compilation, device == 1 the device compilation (one thread per row on the default stream of the current device).
+extern "C++" {
+namespace {
+__global__ void k_lm_scalars(long long n, const double* __restrict__ in, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) satba_lm::lm_scalars_row(in + 6 * i, out + 6 * i);
+}
+}  // namespace
+}  // extern "C++"
+int satba_lm_scalars(int32_t device, int64_t n, const double* in, double* out) {
+    if (device != 0 && device != 1) return fail(SATBA_E_ARG, "device must be 0 (host compilation) or 1 (device compilation)");
+    if (n < 0 || n > (1ll << 24)) return fail(SATBA_E_ARG, "between 0 and 2^24 rows");
+    if (n == 0) return 0;
+    if (!in || !out) return fail(SATBA_E_ARG, "null argument");
+    if (device == 0) {
+        for (int64_t i = 0; i < n; ++i) satba_lm::lm_scalars_row(in + 6 * i, out + 6 * i);
+        return 0;
+    }
+    const size_t bytes = sizeof(double) * 6 * (size_t)n;
+    double *d_in = nullptr, *d_out = nullptr;
+    const int rc = [&]() -> int {
+        HIP_TRY(hipMalloc((void**)&d_in, bytes));
+        HIP_TRY(hipMalloc((void**)&d_out, bytes));
+        HIP_TRY(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_lm_scalars, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t) nullptr, (long long)n, d_in, d_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));  // (waits for the kernel: the default stream)
+        return 0;
+    }();
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}

@@ -30,7 +30,7 @@ SYMBOLS = [
     "satba_accept", "satba_camera_sums_fallback", "satba_read_header", "satba_get_blocks", "satba_get_jacobian", "satba_get_exchange",
     "satba_set_exchange", "satba_get_vector", "satba_time_kernel",
     "satba_packed_schur_len", "satba_pack_schur", "satba_solve_messages", "satba_solve_messages_bind", "satba_solve_messages_begin", "satba_solve_messages_arrived", "satba_solve_messages_end", "satba_unpack_schur",
-    "satba_solve_lm", "satba_lm_step", "satba_lm_run", "satba_lm_state", "satba_lm_begin", "satba_lm_part", "satba_lm_poll", "satba_profile_linearize", "satba_profile_read", "satba_outliers", "satba_layout_len", "satba_get_layout", "satba_get_info",
+    "satba_solve_lm", "satba_lm_step", "satba_lm_run", "satba_lm_state", "satba_lm_begin", "satba_lm_part", "satba_lm_poll", "satba_lm_scalars", "satba_profile_linearize", "satba_profile_read", "satba_outliers", "satba_layout_len", "satba_get_layout", "satba_get_info",
     "satba_triangulate_pairwise", "satba_init_pts3d", "satba_init_pts3d_resident", "satba_snapshot_x",
     "satba_rpc_fit", "satba_rpc_localization", "satba_rpc_refit",
     "satba_rpc_affine_approx", "satba_rpc_perspective_approx", "satba_camera_resection", "satba_rpc_mesh",
@@ -138,6 +138,7 @@ def load_library(path=None):
     lib.satba_lm_part.argtypes = [h, C.c_int32, C.c_double]
     lib.satba_lm_poll.argtypes = [h, C.POINTER(C.c_int64), C.c_int32]
     lib.satba_lm_state.argtypes = [h, C.POINTER(C.c_double), C.c_int32]
+    lib.satba_lm_scalars.argtypes = [C.c_int32, C.c_int64, _dp, _dp]
     lib.satba_profile_linearize.argtypes = [h, C.c_int32]
     lib.satba_profile_read.argtypes = [h, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.satba_outliers.argtypes = [h, _dp, C.c_double, C.c_double, _dp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]
@@ -204,6 +205,16 @@ def check_predef_thr(predef_thr):
     """satba_outliers takes predef_thr < 0 as "no predefined threshold": a caller's negative or NaN value must not reach it."""
     if predef_thr is not None and not float(predef_thr) >= 0.0:
         raise ValueError("predef_thr must be None or a non-negative number, got {!r}".format(predef_thr))
+
+
+def lm_scalars(rows, device):
+    """satba_lm_scalars: rows [n, 6] = a, b, c, g0, g1, Delta -> [n, 6] = p0, p1, newton, Delta_new, ratio, term from the library's host
+    compilation of csrc/satba_lm.h (device False) or from its device compilation (device True)."""
+    lib = load_library()
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 6)
+    out = np.empty_like(rows)
+    _check(lib, lib.satba_lm_scalars(int(bool(device)), rows.shape[0], _ptr(rows), _ptr(out)))
+    return out
 
 
 class HipEngine:

@@ -38,6 +38,7 @@ Engine contract (implemented by engine_hip.HipEngine; tests use a CPU stand-in b
 """
 import math
 import os
+import sys
 
 import numpy as np
 
@@ -233,14 +234,30 @@ def solve_trust_region_2d(B, g, Delta):
     latter among the real roots of a quartic (numpy.roots, ~60 us per call, with the device idle); the same point is
     the solution of the secular equation |(B + mu I)^-1 g| = Delta, mu >= max(0, -lambda_min(B)), solved here in the
     eigenbasis of B with Newton's method on 1/|p(mu)| - 1/Delta (monotone and concave on that interval), plain
-    Python floats.
+    Python floats.  Branch for branch csrc/satba_lm.h:solve_trust_region_2d, singular models included (DESIGN.md,
+    "The trust-region scalars at singular models").
     """
+    g0, g1, Delta = float(g[0]), float(g[1]), float(Delta)
+    if not Delta > 0:  # no radius, no step
+        return np.array([0.0, 0.0]), False
     a, b, c = float(B[0, 0]), float(B[0, 1]), float(B[1, 1])
-    g0, g1 = float(g[0]), float(g[1])
-    det = a * c - b * b
-    if a > 0 and det > 0:  # positive definite: try the Newton step
+    if not Delta < 2.0 ** -480:
+        return _tr2d_scaled(a, b, c, g0, g1, Delta)
+    # the squares of Delta and of the step underflow: the same model in the variables 2^600 p, its value times 2^900
+    s = 2.0 ** 300
+    p, newton = _tr2d_scaled(a / s, b / s, c / s, g0 * s, g1 * s, Delta * s * s)
+    return p / s / s, newton
+
+
+def _tr2d_scaled(a, b, c, g0, g1, Delta):
+    ac = a * c
+    det = ac - b * b
+    # thin: det lost more than 26 of its 53 bits to cancellation, the Newton step below would be noise over noise
+    thin = a > 0 and det > 0 and not det > 2.0 ** -26 * ac
+    if a > 0 and det > 0 and not thin:  # positive definite: try the Newton step
         p0, p1 = -(c * g0 - b * g1) / det, -(a * g1 - b * g0) / det
-        if p0 * p0 + p1 * p1 <= Delta * Delta:
+        n2 = p0 * p0 + p1 * p1
+        if n2 <= Delta * Delta and n2 <= sys.float_info.max:
             return np.array([p0, p1]), True
     # eigen-decomposition B = l1 v1 v1^T + l2 v2 v2^T, l1 <= l2
     h, d = 0.5 * (a + c), 0.5 * (a - c)
@@ -256,6 +273,11 @@ def solve_trust_region_2d(B, g, Delta):
         v1x, v1y = (d - r) / n, b / n
     v2x, v2y = -v1y, v1x
     c1, c2 = g0 * v1x + g1 * v1y, g0 * v2x + g1 * v2y  # g in the eigenbasis
+    if thin and l1 > 0:  # the Newton step of the model the eigenbasis stands for
+        q1, q2 = -c1 / l1, -c2 / l2
+        n2 = q1 * q1 + q2 * q2
+        if n2 <= Delta * Delta and n2 <= sys.float_info.max:
+            return np.array([q1 * v1x + q2 * v2x, q1 * v1y + q2 * v2y]), True
     gn = math.hypot(c1, c2)
     if gn == 0.0:  # no gradient: along the eigenvector of the smallest eigenvalue
         return np.array([Delta * v1x, Delta * v1y]), False
@@ -265,6 +287,8 @@ def solve_trust_region_2d(B, g, Delta):
     if abs(c1) <= tiny and l2 + lo > 0 and abs(c2) / (l2 + lo) < Delta:
         q2 = -c2 / (l2 + lo)
         q1 = math.sqrt(max(Delta * Delta - q2 * q2, 0.0))
+        if c1 > 0:  # what there is of a gradient along v1 decides between the two minimisers
+            q1 = -q1
         return np.array([q1 * v1x + q2 * v2x, q1 * v1y + q2 * v2y]), False
     # |p(mu)| <= |g| / (l1 + mu): the root lies in [lo, |g| / Delta - l1].  Newton on phi = 1/|p| - 1/Delta from the
     # upper end, safeguarded by the bracket
@@ -273,7 +297,10 @@ def solve_trust_region_2d(B, g, Delta):
     for _ in range(100):
         d1, d2 = l1 + mu, l2 + mu
         if d1 <= 0.0:
-            mu = 0.5 * (mu_lo + mu_hi)
+            mid = 0.5 * (mu_lo + mu_hi)
+            if mid == mu:  # a bracket of one point
+                break
+            mu = mid
             continue
         q1, q2 = c1 / d1, c2 / d2
         n2 = q1 * q1 + q2 * q2
@@ -294,7 +321,14 @@ def solve_trust_region_2d(B, g, Delta):
                 break
         mu = new
     d1, d2 = l1 + mu, l2 + mu
-    q1, q2 = -c1 / d1, -c2 / d2
+    if d1 > 0.0:
+        q1, q2 = -c1 / d1, -c2 / d2
+    else:  # mu = -l1 to the last bit: what is left of Delta goes along v1, down the gradient
+        q2 = -c2 / d2 if d2 > 0.0 else 0.0
+        t = q2 / Delta
+        q1 = Delta * math.sqrt((1.0 - t) * (1.0 + t)) if abs(t) < 1.0 else 0.0
+        if c1 > 0:
+            q1 = -q1
     s = Delta / math.hypot(q1, q2)  # exactly on the boundary
     q1, q2 = q1 * s, q2 * s
     return np.array([q1 * v1x + q2 * v2x, q1 * v1y + q2 * v2y]), False

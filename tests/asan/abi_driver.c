@@ -68,6 +68,16 @@ int main(void) {
     CHECK(satba_rpc_localization(NULL, 3, NULL, NULL, NULL, NULL, NULL, 0) == SATBA_E_ARG);
     CHECK(satba_triangulate_pairwise(SATBA_RPC, NULL, NULL, 1, NULL, NULL, NULL, NULL, 0, NULL) == SATBA_E_ARG);
     CHECK(satba_init_pts3d(SATBA_AFFINE, 2, 1, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL, 0, 1, NULL) == SATBA_E_ARG);
+    {   /* the scalar side of the loop: argument checks, then the host compilation on the stalled bracket, a rank-one model and no radius */
+        double in[18] = {-1, 0, 1, 1e-20, 0, 1, 1, 2, 4, -1, -2, 8, 2, 0, 1, 1, 1, 0}, out[18];
+        CHECK(satba_lm_scalars(2, 1, in, out) == SATBA_E_ARG && satba_lm_scalars(0, -1, in, out) == SATBA_E_ARG);
+        CHECK(satba_lm_scalars(0, 1, NULL, out) == SATBA_E_ARG && satba_lm_scalars(1, 1, in, NULL) == SATBA_E_ARG);
+        CHECK(satba_lm_scalars(0, 0, NULL, NULL) == SATBA_OK && satba_lm_scalars(1, 0, NULL, NULL) == SATBA_OK);
+        CHECK(satba_lm_scalars(0, 3, in, out) == SATBA_OK);
+        CHECK(out[0] == -1.0 && out[1] == 0.0 && out[2] == 0.0);
+        CHECK(out[6] == out[6] && out[7] == out[7] && out[6] * out[6] + out[7] * out[7] <= 64.0 * (1.0 + 1e-15));
+        CHECK(out[12] == 0.0 && out[13] == 0.0 && out[14] == 0.0);
+    }
     satba_problem_destroy(NULL);
     printf("abi_driver ok\n");
     return 0;
