@@ -522,6 +522,29 @@ int satba_camera_resection(int32_t n_cam, int32_t n_pts, const double *X, const 
 int satba_rpc_mesh(int32_t n_cam, const double *tables, const double *col_range, const double *row_range, const double *alt_range,
                    int32_t n_col, int32_t n_row, int32_t n_alt, double *X_out, double *x_out, double *alt_out, int32_t device);
 
+/* ---- affine fundamental matrices of image pairs from their RPCs, the step between the choice of the pairs and their matching
+ * under the epipolar gate (ft_pipeline.py:139-152, init_F_pair_to_match).  Stand-alone: no problem handle, float64, all pairs of a
+ * call in one launch, the tables uploaded once.  Like the entries above it left the version number unchanged.
+ * Per pair (i, j) of `pairs` (n_pairs x 2, indices into the n_cam tables) and its region of interest roi (n_pairs x 4: x, y, w, h in
+ * image i) the matches of s2p.rpc_utils.matches_from_rpc (rpc_utils.py:199-246): an n x n x n mesh (numpy.linspace over columns
+ * [x + w / 2n, x + (2n - 1) w / 2n], rows likewise, altitudes alt_offset -+ alt_scale of RPC i; columns fastest, altitudes
+ * slowest) is localised through RPC i and projected through both RPCs -> rows x1, y1, x2, y2; then
+ * s2p.estimation.affine_fundamental_matrix (estimation.py:114-154) of them: N, the right singular vector of the smallest singular
+ * value of A = X - mean, X = (x2, y2, x1, y1), taken as the eigenvector of A^T A.  2 <= n <= 11 (the reference uses 5).
+ * Outputs: F5 (n_pairs x 5) = F02, F12, F20, F21 = N of unit length and F22 = -N . mean, every other entry of the 3 x 3 matrix being
+ * zero; sv (n_pairs x 4, may be NULL): the singular values of A, descending; matches (n_pairs x n^3 x 4, may be NULL).
+ * Sign: the component of N with the largest magnitude is positive.  The sign the reference returns is an accident of LAPACK's SVD
+ * and flips between crops of one pair; it means nothing, the epipolar gate of the match entry above is the same for F and -F.
+ * Degenerate pairs (an image paired with itself, two identical RPCs: the second smallest eigenvalue of A^T A is not above 1e-12
+ * of the largest, so no unique N exists): with degenerate == NULL the call returns SATBA_E_NONFINITE and writes no output; with
+ * degenerate (n_pairs) given it succeeds, degenerate[p] = 1 marks those pairs and their F5 is NaN.
+ * SATBA_E_ARG: a null pointer, a negative count, n outside 2..11, a pair index outside 0..n_cam-1, w <= 0 or h <= 0.
+ * SATBA_E_NONFINITE: a non-finite table or region.  n_pairs == 0 returns 0 without a device call.
+ * The kernel_ms entry returns the kernel time (HIP events, milliseconds) of the calling thread's last successful call. */
+int satba_rpc_fundamental(int32_t n_cam, const double *tables, int32_t n_pairs, const int32_t *pairs, const double *roi, int32_t n,
+                          double *F5, double *sv, double *matches, uint8_t *degenerate, int32_t device);
+double satba_rpc_fundamental_kernel_ms(void);
+
 /* ---- inspection entry points (parity tests; not used by the solver loop) */
 /* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64): n must equal satba_layout_len */
 enum { SATBA_LAY_PERM = 0, SATBA_LAY_RANK, SATBA_LAY_PT_CNT, SATBA_LAY_SLICE_BASE, SATBA_LAY_E_CAM, SATBA_LAY_OBS_POS, SATBA_LAY_CAM_OFS,

@@ -59,17 +59,18 @@ __device__ inline void cam_mesh_node(const T& tab, const double* cr, const doubl
     refit_to_ecef(lat, lon, alt, p[0], p[1], p[2]);
 }
 
-// eigenvectors (columns of V) and eigenvalues (diagonal of A) of the symmetric 12 x 12 matrix A by cyclic Jacobi, one lane.  A
-// rotation is skipped once |a_pq| is below 2^-56 of the two diagonal entries: what is left moves an eigenvector by less than one
-// rounding of the gap to its neighbour.  (A^T A is only positive semi-definite up to rounding: its smallest eigenvalue may come
-// out negative, so the test is on the absolute values.)
-__device__ inline void cam_jacobi12(double (*A)[12], double (*V)[12]) {
-    for (int r = 0; r < 12; ++r)
-        for (int c = 0; c < 12; ++c) V[r][c] = r == c ? 1.0 : 0.0;
+// eigenvectors (columns of V) and eigenvalues (diagonal of A) of the symmetric N x N matrix A by cyclic Jacobi, one lane (12 x 12:
+// the resection below, "cam_jacobi12" in tests/cases_camapprox.py; 4 x 4: satba_fundamental.h).  A rotation is skipped once |a_pq| is below 2^-56 of the two diagonal entries:
+// what is left moves an eigenvector by less than one rounding of the gap to its neighbour.  (A^T A is only positive semi-definite
+// up to rounding: its smallest eigenvalue may come out negative, so the test is on the absolute values.)
+template <int N>
+__device__ inline void cam_jacobi(double (*A)[N], double (*V)[N]) {
+    for (int r = 0; r < N; ++r)
+        for (int c = 0; c < N; ++c) V[r][c] = r == c ? 1.0 : 0.0;
     for (int sweep = 0; sweep < CAM_SWEEPS; ++sweep) {
         bool rotated = false;
-        for (int p = 0; p < 11; ++p)
-            for (int q = p + 1; q < 12; ++q) {
+        for (int p = 0; p < N - 1; ++p)
+            for (int q = p + 1; q < N; ++q) {
                 const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
                 if (!(fabs(apq) > 0x1p-56 * (fabs(app) + fabs(aqq)))) continue;  // (also: a NaN rotates nothing and stays)
                 rotated = true;
@@ -77,7 +78,7 @@ __device__ inline void cam_jacobi12(double (*A)[12], double (*V)[12]) {
                 const double d = aqq - app, g2 = 2.0 * apq;
                 const double t = copysign(1.0, d) * g2 / (fabs(d) + sqrt(d * d + g2 * g2));
                 const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                for (int k = 0; k < 12; ++k) {
+                for (int k = 0; k < N; ++k) {
                     if (k != p && k != q) {
                         const double akp = A[k][p], akq = A[k][q];
                         A[k][p] = A[p][k] = c * akp - s * akq;
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(CAM_THREADS) void k_cam_resect(const CamResectArgs 
     __syncthreads();
     // ---- (d) the eigenvector of the smallest eigenvalue, (e) P = T^-1 Pn U
     if (tid == 0) {
-        cam_jacobi12(s_A, s_V);
+        cam_jacobi<12>(s_A, s_V);
         int k0 = 0;
         double lmax = s_A[0][0], l2 = INFINITY, sum = 0.0;
         for (int k = 0; k < 12; ++k) {

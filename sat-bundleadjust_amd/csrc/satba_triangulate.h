@@ -133,9 +133,10 @@ struct TriCubic2 {
         xo = r[0] / r[1]; yo = r[2] / r[3];
     }
 };
-// localisation: image (x, y) at height z -> (lon, lat), Newton inversion of the projection (ref:c/rpc.c:372-408, 428-438), delta = 0.1
+// localisation: image (x, y) at height z -> (lon, lat), Newton inversion of the projection (ref:c/rpc.c:372-408, 428-438), delta = 0.1.
+// tol2: the squared normalised residual at which the iteration stops; 1e-18 is the reference's (ref:c/rpc.c:394)
 template <class T>
-__device__ inline void tri_localize(const T& c, double x, double y, double z, double& lon_o, double& lat_o) {
+__device__ inline void tri_localize(const T& c, double x, double y, double z, double& lon_o, double& lat_o, double tol2 = 1e-18) {
     const double xf = (x - c(86)) / c(87), yf = (y - c(88)) / c(89);
     TriCubic2 f;
     f.reduce(c, (z - c(84)) / c(85));
@@ -145,7 +146,7 @@ __device__ inline void tri_localize(const T& c, double x, double y, double z, do
         double x00, x01, x10, x11, x20, x21;
         f.eval(lon, lat, x00, x01);
         const double u0 = xf - x00, u1 = yf - x01;
-        if (!(u0 * u0 + u1 * u1 > 1e-18)) break;
+        if (!(u0 * u0 + u1 * u1 > tol2)) break;
         f.eval(lon + eps, lat, x10, x11); f.eval(lon, lat + eps, x20, x21);
         const double e10 = x10 - x00, e11 = x11 - x01, e20 = x20 - x00, e21 = x21 - x01;
         const double det = e10 * e21 - e11 * e20;

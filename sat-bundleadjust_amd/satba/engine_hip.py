@@ -34,6 +34,7 @@ SYMBOLS = [
     "satba_triangulate_pairwise", "satba_init_pts3d", "satba_init_pts3d_resident", "satba_snapshot_x",
     "satba_rpc_fit", "satba_rpc_localization", "satba_rpc_refit",
     "satba_rpc_affine_approx", "satba_rpc_perspective_approx", "satba_camera_resection", "satba_rpc_mesh",
+    "satba_rpc_fundamental", "satba_rpc_fundamental_kernel_ms",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
     "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
     "satba_match_pairs", "satba_matches_fetch", "satba_matches_destroy",
@@ -154,6 +155,9 @@ def load_library(path=None):
     lib.satba_rpc_perspective_approx.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32]
     lib.satba_camera_resection.argtypes = [C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32]
     lib.satba_rpc_mesh.argtypes = [C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32]
+    lib.satba_rpc_fundamental.argtypes = [C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32]
+    lib.satba_rpc_fundamental_kernel_ms.argtypes = []
+    lib.satba_rpc_fundamental_kernel_ms.restype = C.c_double
     _fp = C.POINTER(C.c_float)
     lib.satba_triangulate_pairwise.argtypes = [C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _dp, _fp, C.c_int32, _fp]
     lib.satba_init_pts3d.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, C.c_int32, _ip, _fp, _ip,

@@ -8,6 +8,9 @@ ref:3rdparty/sift/simd/sift4ctypes.cpp:125-195, bit for bit on integer descripto
 and its UTM consistency filter.  All pairs go to the device in one call; there is no CPU fallback: without libsatba_hip.so or
 without a GPU the calls raise.
 
+The fundamental matrices of "epipolar_based" matching come from `fundamental_matrices` (satba/rpc_utils.py, re-exported here): one
+matrix per pair from the two RPCs, all pairs in one device call.
+
 Renaming.  ref:ft_s2p.s2p_match_SIFT maps a match back to indices by its coordinates (`list.index`), so a keypoint is named by the
 first keypoint with the same (col, row) -- SIFT emits one keypoint per orientation at a location.  `canonical=True` (the default)
 reproduces that with one index map per image (keypoints that share a location share their UTM coordinates, so they are inside a
@@ -25,6 +28,7 @@ from . import engine_hip as E
 from . import geo_utils
 from .ba_outliers import get_elbow_value
 from .ft_triangulate import _device
+from .rpc_utils import affine_fundamental_matrix, fundamental_matrices, matches_from_rpc  # noqa: F401  (the pairs' matrices: the step in front)
 
 _lp = ct.POINTER(ct.c_int64)
 _fp = ct.POINTER(ct.c_float)
