@@ -7,7 +7,9 @@
 // More than 63 unknowns: ONE persistent launch factorises the matrix in 64 x 64 tiles and carries the right-hand side along
 // (k_chol_tiles, satba_chol3.h), then the multi-workgroup backward substitution (k_trsv_back_mw).  Up to 63 unknowns (the
 // reference's usual 2 .. 20 images x 3 parameters): the whole solve phase is one workgroup (k_solve_small, satba_chol3.h) and never
-// comes here; n_c = (cameras) x (3, 5 or 6) is never 64.  The panel-step kernels of rounds 1 - 2 were removed in round 5.
+// comes here.  n_c = (cameras) x (3, 5, 6, 8 or 11): with the intrinsics refined (8 or 11 unknowns per camera) n_c = 64 exists -- 8 affine
+// cameras -- and takes the tile kernel with ONE tile (as do 128, 256 and 1024, the last size of the multi-workgroup substitution).
+// The panel-step kernels of rounds 1 - 2 were removed in round 5.
 // fp64 MFMA runs at the vector rate on gfx950 and the matrix is tiny: the solve is bound by the latency of the
 // dependent pivot chain (tools/ubench/dp_latency.hip: 92 ns per column at best), not by flops; see DESIGN.md.
 #pragma once
