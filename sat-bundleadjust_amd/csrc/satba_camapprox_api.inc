@@ -2,11 +2,6 @@
 // extern "C" block of satba_capi.hip; stand-alone (no handle)
 extern "C++" {
 namespace {
-bool cam_all_finite(const double* v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
 // results reach the caller only when every one of them is finite: a degenerate camera is an error code, never a NaN matrix
 int cam_hand_over(const std::vector<double>& h, size_t n_cam, double* P_out, double* mean_err, double* centers) {
     if (!cam_all_finite(h.data(), h.size())) return fail(SATBA_E_NONFINITE, "Singular matrix: degenerate points, no camera fits them");
@@ -28,9 +23,9 @@ int cam_mesh_check(int32_t n_cam, const double* tables, const double* col_range,
     }
     return 0;
 }
-int cam_launch_resect(TriScratch& s, CamResectArgs& a, int n_cam, double* P_out, double* mean_err, double* centers) {
+int cam_launch_resect(DevRun& s, CamResectArgs& a, int n_cam, double* P_out, double* mean_err, double* centers) {
     double* d_out;
-    TRY(s.upload(&d_out, (const double*)nullptr, (size_t)n_cam * 16));
+    TRY(s.alloc(&d_out, (size_t)n_cam * 16));
     a.P = d_out; a.mean_err = d_out + (size_t)n_cam * 12; a.centers = d_out + (size_t)n_cam * 13; a.alts = nullptr;
     const size_t lds_b = a.n_pts <= CAM_LDS_PTS ? sizeof(double) * 5 * (size_t)a.n_pts : 0;
     if (lds_b > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_cam_resect<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
@@ -50,11 +45,11 @@ int satba_rpc_affine_approx(int32_t n_cam, const double* tables, const double* x
     if (!cam_all_finite(tables, (size_t)n_cam * 90) || !cam_all_finite(xyz, (size_t)n_cam * 3) || !cam_all_finite(col0row0, (size_t)n_cam * 2))
         return fail(SATBA_E_NONFINITE, "non-finite input");
     if (n_cam == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     double *d_tab, *d_xyz, *d_c0, *d_P;
     TRY(s.upload(&d_tab, tables, (size_t)n_cam * 90)); TRY(s.upload(&d_xyz, xyz, (size_t)n_cam * 3)); TRY(s.upload(&d_c0, col0row0, (size_t)n_cam * 2));
-    TRY(s.upload(&d_P, (const double*)nullptr, (size_t)n_cam * 12));
+    TRY(s.alloc(&d_P, (size_t)n_cam * 12));
     hipLaunchKernelGGL(k_cam_affine, dim3((n_cam + CAM_THREADS - 1) / CAM_THREADS), dim3(CAM_THREADS), 0, s.stream, n_cam, d_tab, d_xyz, d_c0, d_P);
     HIP_TRY(hipGetLastError());
     std::vector<double> h((size_t)n_cam * 12);
@@ -70,7 +65,7 @@ int satba_rpc_perspective_approx(int32_t n_cam, const double* tables, const doub
     if (!P_out) return fail(SATBA_E_ARG, "null argument");
     if (crop0 && !cam_all_finite(crop0, (size_t)n_cam * 2)) return fail(SATBA_E_NONFINITE, "non-finite crop offset");
     if (n_cam == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     CamResectArgs a{};
     a.n_pts = n_col * n_row * n_alt; a.n_col = n_col; a.n_row = n_row; a.n_alt = n_alt;
@@ -80,7 +75,7 @@ int satba_rpc_perspective_approx(int32_t n_cam, const double* tables, const doub
     if (crop0) TRY(s.upload(&d_c0, crop0, (size_t)n_cam * 2));
     a.tables = d_tab; a.col_range = d_cr; a.row_range = d_rr; a.alt_range = d_ar; a.crop0 = d_c0;
     if (a.n_pts > CAM_LDS_PTS) {  // the mesh does not fit the LDS: a slab per camera
-        TRY(s.upload(&a.X, (const double*)nullptr, (size_t)n_cam * a.n_pts * 3)); TRY(s.upload(&a.x, (const double*)nullptr, (size_t)n_cam * a.n_pts * 2));
+        TRY(s.alloc(&a.X, (size_t)n_cam * a.n_pts * 3)); TRY(s.alloc(&a.x, (size_t)n_cam * a.n_pts * 2));
     }
     return cam_launch_resect(s, a, n_cam, P_out, mean_err, centers);
 }
@@ -90,7 +85,7 @@ int satba_camera_resection(int32_t n_cam, int32_t n_pts, const double* X, const 
     if (n_pts < 6 || n_pts > CAM_MAX_PTS) return fail(SATBA_E_ARG, "a resection needs 6 to %d correspondences", CAM_MAX_PTS);
     if (!cam_all_finite(X, (size_t)n_cam * n_pts * 3) || !cam_all_finite(x, (size_t)n_cam * n_pts * 2)) return fail(SATBA_E_NONFINITE, "non-finite point");
     if (n_cam == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     CamResectArgs a{};
     a.n_pts = n_pts;
@@ -103,7 +98,7 @@ int satba_rpc_mesh(int32_t n_cam, const double* tables, const double* col_range,
     TRY(cam_mesh_check(n_cam, tables, col_range, row_range, alt_range, n_col, n_row, n_alt));
     if (!X_out || !x_out) return fail(SATBA_E_ARG, "null argument");
     if (n_cam == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     CamResectArgs a{};
     a.n_pts = n_col * n_row * n_alt; a.n_col = n_col; a.n_row = n_row; a.n_alt = n_alt;
@@ -112,7 +107,7 @@ int satba_rpc_mesh(int32_t n_cam, const double* tables, const double* col_range,
     TRY(s.upload(&d_tab, tables, (size_t)n_cam * 90)); TRY(s.upload(&d_cr, col_range, (size_t)n_cam * 2)); TRY(s.upload(&d_rr, row_range, (size_t)n_cam * 2));
     TRY(s.upload(&d_ar, alt_range, (size_t)n_cam * 2));
     a.tables = d_tab; a.col_range = d_cr; a.row_range = d_rr; a.alt_range = d_ar;
-    TRY(s.upload(&a.X, (const double*)nullptr, n * 3)); TRY(s.upload(&a.x, (const double*)nullptr, n * 2)); TRY(s.upload(&a.alts, (const double*)nullptr, n));
+    TRY(s.alloc(&a.X, n * 3)); TRY(s.alloc(&a.x, n * 2)); TRY(s.alloc(&a.alts, n));
     hipLaunchKernelGGL(k_cam_resect<true>, dim3(n_cam), dim3(CAM_THREADS), 0, s.stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(X_out, a.X, sizeof(double) * n * 3, hipMemcpyDeviceToHost, s.stream));

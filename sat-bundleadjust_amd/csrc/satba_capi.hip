@@ -228,6 +228,8 @@ static int dev_alloc(satba_problem* p, T** out, size_t count) {
         if (rc_) return rc_; \
     } while (0)
 
+#include "satba_devmem.h"
+
 // dispatch on (camera model, parameters per camera, camera table in LDS, RPC table in LDS); valid pairs: affine {3,5,8},
 // perspective {3,6,11}, rpc {3,6}
 #define SATBA_CASE(key, M_, NP_, CL_, RL_, ...)                                                                    \
@@ -619,53 +621,47 @@ static int ensure_wlayout(satba_problem* p) {
     // each -- a track is at most M observations long (cameras strictly ascending inside a point)
     if ((long long)p->K + 13LL * N + 8 >= (1LL << 31)) return fail(SATBA_E_ARG, "the merged records of this shard exceed 2^31 pieces");
     if (M >= 65536) return fail(SATBA_E_ARG, "the merged record layout holds track positions in 16 bits: fewer than 65 536 cameras");
-    int rc = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&sz, sizeof(int) * (Nz + 1)));  // (freed below whatever fails from here on)
-        HIP_TRY(hipMalloc((void**)&wb, sizeof(int) * (Nz + 1)));
-        TRY(dev_alloc(p, &L.w_fix, Nz)); TRY(dev_alloc(p, &L.sc_ofs, Nz));
-        HIP_TRY(hipMemsetAsync(sz, 0, sizeof(int) * (Nz + 1), st));
-        hipLaunchKernelGGL(k_lay_wsize, dim3((unsigned)((Nz + 255) / 256)), dim3(256), 0, st, N, L.pt_cnt, sz);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sz, wb, (int)(Nz + 1), st));
-        HIP_TRY(hipMalloc((void**)&cub, need + 16));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, sz, wb, (int)(Nz + 1), st));
-        hipLaunchKernelGGL(k_lay_wfix, dim3((unsigned)((Nz + 255) / 256)), dim3(256), 0, st, N, L.pt_cnt, sz, wb, L.w_fix, L.sc_ofs);
-        int h_len = 0, h_zero = 0;
-        HIP_TRY(hipMemcpyAsync(&h_len, wb + Nz, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&h_zero, L.w_fix + N, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        // (32-bit piece offsets: 2^31 pieces are 32 GB of records; a shard has fewer than 2^31 observations)
-        if (h_len <= 0) return fail(SATBA_E_ARG, "the merged records of this shard exceed 2^31 pieces");
-        L.W_len = h_len; L.zero_fix = h_zero;
-        TRY(dev_alloc(p, &p->d_W, (size_t)L.W_len + 8));
-        HIP_TRY(hipMemsetAsync(p->d_W, 0, sizeof(double2) * ((size_t)L.W_len + 8), st));  // pads, the zero record; scales are 0 until a linearisation
-        const size_t Ez = (size_t)std::max<long long>(L.E, 1), Kz = (size_t)std::max<long long>(p->K, 1);
-        TRY(dev_alloc(p, &L.pair_rec, Ez)); TRY(dev_alloc(p, &L.pair_kk, Ez)); TRY(dev_alloc(p, &L.cm_rec, Kz)); TRY(dev_alloc(p, &L.cm_sc, Kz));
-        if (L.E > 0)
-            hipLaunchKernelGGL(k_lay_pair_w, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, L.pair_pts, L.pair_pi, L.pair_pj, L.ipt_ofs, L.pt_cnt,
-                               L.w_fix, L.pair_rec, L.pair_kk);
-        if (p->K > 0)
-            hipLaunchKernelGGL(k_lay_cm_w, dim3(grid_for(p->K, 256, 8192)), dim3(256), 0, st, p->K, L.cm_pt, L.cm_io, L.ipt_ofs, L.pt_cnt, L.w_fix,
-                               L.cm_rec, L.cm_sc);
-        // diagonal items: about 768 entries each (a dozen iterations of a wave; the pair items of the headline shape run five), at most 64
-        // per camera (k_schur_finish adds a camera's partials with eight threads)
-        const int C = L.C;
-        const long long per_group = p->K / std::max(1, M) / std::max(1, C);
-        int spc = (int)std::max<long long>(1, std::min<long long>((per_group + 767) / 768, std::max(1, 64 / C)));
-        if (const char* e = getenv("SATBA_DIAG_SPC")) spc = std::max(1, std::min(atoi(e), std::max(1, 64 / C)));  // experiments
-        L.dg_spc = spc; L.n_dg = C * spc;
-        TRY(dev_alloc(p, &L.dg_ofs, (size_t)M * L.n_dg + 1));
-        hipLaunchKernelGGL(k_lay_diag_items, dim3((unsigned)((M * C + 1 + 255) / 256)), dim3(256), 0, st, M, C, spc, std::max(N, 1), L.cam_ofs, L.cm_pt, L.dg_ofs);
-        HIP_TRY(hipGetLastError());
-        // what a camera's diagonal items weigh when the rows are dealt to the XCDs, in pair items: its entries over those of a pair
-        const long long dg_weight = std::max<long long>(1, pairs_run(p) ? (long long)((double)p->K / M / ((double)L.E / L.n_pairs)) : 1);
-        TRY(schur_items_build(p, SCHUR_ITEMS_WEIGHTED, &p->items_w, dg_weight));
-        HIP_TRY(hipStreamSynchronize(st));
-        return 0;
-    }();
-    if (sz) (void)hipFree(sz);
-    if (wb) (void)hipFree(wb);
-    if (cub) (void)hipFree(cub);
-    if (rc) return rc;
+    DevAllocs tmp;  // sz, wb and cub: gone when this returns
+    TRY(tmp.alloc(&sz, Nz + 1));
+    TRY(tmp.alloc(&wb, Nz + 1));
+    TRY(dev_alloc(p, &L.w_fix, Nz)); TRY(dev_alloc(p, &L.sc_ofs, Nz));
+    HIP_TRY(hipMemsetAsync(sz, 0, sizeof(int) * (Nz + 1), st));
+    hipLaunchKernelGGL(k_lay_wsize, dim3((unsigned)((Nz + 255) / 256)), dim3(256), 0, st, N, L.pt_cnt, sz);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sz, wb, (int)(Nz + 1), st));
+    TRY(tmp.alloc(&cub, need + 16));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, sz, wb, (int)(Nz + 1), st));
+    hipLaunchKernelGGL(k_lay_wfix, dim3((unsigned)((Nz + 255) / 256)), dim3(256), 0, st, N, L.pt_cnt, sz, wb, L.w_fix, L.sc_ofs);
+    int h_len = 0, h_zero = 0;
+    HIP_TRY(hipMemcpyAsync(&h_len, wb + Nz, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_zero, L.w_fix + N, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // (32-bit piece offsets: 2^31 pieces are 32 GB of records; a shard has fewer than 2^31 observations)
+    if (h_len <= 0) return fail(SATBA_E_ARG, "the merged records of this shard exceed 2^31 pieces");
+    L.W_len = h_len; L.zero_fix = h_zero;
+    TRY(dev_alloc(p, &p->d_W, (size_t)L.W_len + 8));
+    HIP_TRY(hipMemsetAsync(p->d_W, 0, sizeof(double2) * ((size_t)L.W_len + 8), st));  // pads, the zero record; scales are 0 until a linearisation
+    const size_t Ez = (size_t)std::max<long long>(L.E, 1), Kz = (size_t)std::max<long long>(p->K, 1);
+    TRY(dev_alloc(p, &L.pair_rec, Ez)); TRY(dev_alloc(p, &L.pair_kk, Ez)); TRY(dev_alloc(p, &L.cm_rec, Kz)); TRY(dev_alloc(p, &L.cm_sc, Kz));
+    if (L.E > 0)
+        hipLaunchKernelGGL(k_lay_pair_w, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, L.pair_pts, L.pair_pi, L.pair_pj, L.ipt_ofs, L.pt_cnt,
+                           L.w_fix, L.pair_rec, L.pair_kk);
+    if (p->K > 0)
+        hipLaunchKernelGGL(k_lay_cm_w, dim3(grid_for(p->K, 256, 8192)), dim3(256), 0, st, p->K, L.cm_pt, L.cm_io, L.ipt_ofs, L.pt_cnt, L.w_fix,
+                           L.cm_rec, L.cm_sc);
+    // diagonal items: about 768 entries each (a dozen iterations of a wave; the pair items of the headline shape run five), at most 64
+    // per camera (k_schur_finish adds a camera's partials with eight threads)
+    const int C = L.C;
+    const long long per_group = p->K / std::max(1, M) / std::max(1, C);
+    int spc = (int)std::max<long long>(1, std::min<long long>((per_group + 767) / 768, std::max(1, 64 / C)));
+    if (const char* e = getenv("SATBA_DIAG_SPC")) spc = std::max(1, std::min(atoi(e), std::max(1, 64 / C)));  // experiments
+    L.dg_spc = spc; L.n_dg = C * spc;
+    TRY(dev_alloc(p, &L.dg_ofs, (size_t)M * L.n_dg + 1));
+    hipLaunchKernelGGL(k_lay_diag_items, dim3((unsigned)((M * C + 1 + 255) / 256)), dim3(256), 0, st, M, C, spc, std::max(N, 1), L.cam_ofs, L.cm_pt, L.dg_ofs);
+    HIP_TRY(hipGetLastError());
+    // what a camera's diagonal items weigh when the rows are dealt to the XCDs, in pair items: its entries over those of a pair
+    const long long dg_weight = std::max<long long>(1, pairs_run(p) ? (long long)((double)p->K / M / ((double)L.E / L.n_pairs)) : 1);
+    TRY(schur_items_build(p, SCHUR_ITEMS_WEIGHTED, &p->items_w, dg_weight));
+    HIP_TRY(hipStreamSynchronize(st));
     L.wl_ready = true;
     return 0;
 }
@@ -684,176 +680,165 @@ static int build_layout(satba_problem* p, const satba_problem_desc* d) {
     if (L.n_pairs >= (1ll << 31)) return fail(SATBA_E_ARG, "too many camera pairs");
     auto t0 = std::chrono::steady_clock::now();
 
-    // temporaries of the build (freed at the end)
-    std::vector<void*> tmp;
-    auto tmp_alloc = [&](void** out, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(out, bytes ? bytes : 1));
-        tmp.push_back(*out);
-        return 0;
-    };
-    auto free_tmp = [&]() { for (void* q : tmp) (void)hipFree(q); tmp.clear(); };
-#define TMP(ptr, count) TRY(tmp_alloc((void**)&(ptr), sizeof(*(ptr)) * (size_t)(count)))
-    int rc = [&]() -> int {
-        int *o_cam = nullptr, *flags = nullptr, *o_ofs = nullptr, *cnt_o = nullptr, *iota = nullptr, *slots = nullptr;
-        double2* o_obs = nullptr;
-        double* o_w = nullptr;
-        long long* hits = nullptr;
-        const size_t Kz = (size_t)std::max<long long>(K, 1), Nz = (size_t)std::max(N, 1);
-        TMP(o_cam, Kz); TMP(o_obs, Kz); TMP(o_w, Kz); TMP(flags, 4); TMP(o_ofs, Nz + 1); TMP(cnt_o, Nz); TMP(iota, Nz);
-        TMP(slots, L.n_slices + 1); TMP(hits, Nz + 1);
-        TRY(dev_alloc(p, &L.ipt_ofs, Nz + 1)); TRY(dev_alloc(p, &L.cm_io, Kz));
-        int* ipt_ofs = L.ipt_ofs;
-        TRY(dev_alloc(p, &L.pts_ind, Kz)); TRY(dev_alloc(p, &L.obs_pos, Kz));
-        TRY(dev_alloc(p, &L.perm, Nz)); TRY(dev_alloc(p, &L.rank, Nz)); TRY(dev_alloc(p, &L.pt_cnt, Nz));
-        TRY(dev_alloc(p, &L.slice_base, L.n_slices + 1)); TRY(dev_alloc(p, &L.hit_ofs, Nz + 1));
-        TRY(dev_alloc(p, &L.cam_ofs, M + 1)); TRY(dev_alloc(p, &L.cm_pt, Kz)); TRY(dev_alloc(p, &L.cm_pos, Kz));
-        HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
-        if (K) {
-            HIP_TRY(hipMemcpyAsync(o_cam, d->cam_ind, sizeof(int) * K, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(L.pts_ind, d->pts_ind, sizeof(int) * K, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(o_obs, d->pts2d, sizeof(double) * 2 * K, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(o_w, d->weights, sizeof(double) * K, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_lay_validate, dim3(grid_for(K, 256, 4096)), dim3(256), 0, st, K, M, N, o_cam, L.pts_ind, o_w, flags);
-        }
-        p->create_ms[0] = ms_since(t0);  // uploads queued (pageable host memory: the copies are synchronous in effect)
-        // point CSR of the caller's order, track lengths, stable sort by length
-        hipLaunchKernelGGL((k_lay_offsets<int>), dim3(grid_for(K + 1, 256, 4096)), dim3(256), 0, st, K, N, L.pts_ind, o_ofs);
-        if (N) hipLaunchKernelGGL(k_lay_counts, dim3((N + 255) / 256), dim3(256), 0, st, N, o_ofs, cnt_o, iota);
-        size_t cub_bytes = 0, need = 0;
-        int bits_n = 1;
-        while ((1ll << bits_n) <= M) ++bits_n;  // track lengths are <= M
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, cnt_o, L.pt_cnt, iota, L.perm, N, 0, bits_n, st));
-        cub_bytes = std::max(cub_bytes, need);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, slots, L.slice_base, L.n_slices + 1, st));
-        cub_bytes = std::max(cub_bytes, need);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, hits, L.hit_ofs, N + 1, st));
-        cub_bytes = std::max(cub_bytes, need);
-        int *io_cam = nullptr, *io_pos = nullptr, *io_pt = nullptr, *io_iota = nullptr, *cm_key = nullptr, *cm_io = L.cm_io;
-        TMP(io_cam, Kz); TMP(io_pos, Kz); TMP(io_pt, Kz); TMP(io_iota, Kz); TMP(cm_key, Kz);
-        int bits_m = 1;
-        while ((1ll << bits_m) < M) ++bits_m;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, io_cam, cm_key, io_iota, cm_io, (int)K, 0, bits_m, st));
-        cub_bytes = std::max(cub_bytes, need);
-        char* cub = nullptr;
-        TMP(cub, cub_bytes + 16);
+    DevAllocs tmp;  // temporaries of the build: gone when this returns, before satba_problem_create allocates the solver's state
+    int *o_cam = nullptr, *flags = nullptr, *o_ofs = nullptr, *cnt_o = nullptr, *iota = nullptr, *slots = nullptr;
+    double2* o_obs = nullptr;
+    double* o_w = nullptr;
+    long long* hits = nullptr;
+    const size_t Kz = (size_t)std::max<long long>(K, 1), Nz = (size_t)std::max(N, 1);
+    TRY(tmp.alloc(&o_cam, Kz)); TRY(tmp.alloc(&o_obs, Kz)); TRY(tmp.alloc(&o_w, Kz)); TRY(tmp.alloc(&flags, 4));
+    TRY(tmp.alloc(&o_ofs, Nz + 1)); TRY(tmp.alloc(&cnt_o, Nz)); TRY(tmp.alloc(&iota, Nz));
+    TRY(tmp.alloc(&slots, L.n_slices + 1)); TRY(tmp.alloc(&hits, Nz + 1));
+    TRY(dev_alloc(p, &L.ipt_ofs, Nz + 1)); TRY(dev_alloc(p, &L.cm_io, Kz));
+    int* ipt_ofs = L.ipt_ofs;
+    TRY(dev_alloc(p, &L.pts_ind, Kz)); TRY(dev_alloc(p, &L.obs_pos, Kz));
+    TRY(dev_alloc(p, &L.perm, Nz)); TRY(dev_alloc(p, &L.rank, Nz)); TRY(dev_alloc(p, &L.pt_cnt, Nz));
+    TRY(dev_alloc(p, &L.slice_base, L.n_slices + 1)); TRY(dev_alloc(p, &L.hit_ofs, Nz + 1));
+    TRY(dev_alloc(p, &L.cam_ofs, M + 1)); TRY(dev_alloc(p, &L.cm_pt, Kz)); TRY(dev_alloc(p, &L.cm_pos, Kz));
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    if (K) {
+        HIP_TRY(hipMemcpyAsync(o_cam, d->cam_ind, sizeof(int) * K, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(L.pts_ind, d->pts_ind, sizeof(int) * K, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o_obs, d->pts2d, sizeof(double) * 2 * K, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o_w, d->weights, sizeof(double) * K, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_lay_validate, dim3(grid_for(K, 256, 4096)), dim3(256), 0, st, K, M, N, o_cam, L.pts_ind, o_w, flags);
+    }
+    p->create_ms[0] = ms_since(t0);  // uploads queued (pageable host memory: the copies are synchronous in effect)
+    // point CSR of the caller's order, track lengths, stable sort by length
+    hipLaunchKernelGGL((k_lay_offsets<int>), dim3(grid_for(K + 1, 256, 4096)), dim3(256), 0, st, K, N, L.pts_ind, o_ofs);
+    if (N) hipLaunchKernelGGL(k_lay_counts, dim3((N + 255) / 256), dim3(256), 0, st, N, o_ofs, cnt_o, iota);
+    size_t cub_bytes = 0, need = 0;
+    int bits_n = 1;
+    while ((1ll << bits_n) <= M) ++bits_n;  // track lengths are <= M
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, cnt_o, L.pt_cnt, iota, L.perm, N, 0, bits_n, st));
+    cub_bytes = std::max(cub_bytes, need);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, slots, L.slice_base, L.n_slices + 1, st));
+    cub_bytes = std::max(cub_bytes, need);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, hits, L.hit_ofs, N + 1, st));
+    cub_bytes = std::max(cub_bytes, need);
+    int *io_cam = nullptr, *io_pos = nullptr, *io_pt = nullptr, *io_iota = nullptr, *cm_key = nullptr, *cm_io = L.cm_io;
+    TRY(tmp.alloc(&io_cam, Kz)); TRY(tmp.alloc(&io_pos, Kz)); TRY(tmp.alloc(&io_pt, Kz)); TRY(tmp.alloc(&io_iota, Kz)); TRY(tmp.alloc(&cm_key, Kz));
+    int bits_m = 1;
+    while ((1ll << bits_m) < M) ++bits_m;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, io_cam, cm_key, io_iota, cm_io, (int)K, 0, bits_m, st));
+    cub_bytes = std::max(cub_bytes, need);
+    char* cub = nullptr;
+    TRY(tmp.alloc(&cub, cub_bytes + 16));
+    need = cub_bytes;
+    if (N) HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, need, cnt_o, L.pt_cnt, iota, L.perm, N, 0, bits_n, st));
+    HIP_TRY(hipMemsetAsync(slots, 0, sizeof(int) * (L.n_slices + 1), st));
+    HIP_TRY(hipMemsetAsync(hits, 0, sizeof(long long) * (Nz + 1), st));
+    if (N) hipLaunchKernelGGL(k_lay_rank, dim3((N + 255) / 256), dim3(256), 0, st, N, L.perm, L.pt_cnt, L.rank, slots, hits);
+    need = cub_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, slots, L.slice_base, L.n_slices + 1, st));
+    need = cub_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, hits, L.hit_ofs, N + 1, st));
+    // internal point-major CSR: exclusive sum of the sorted lengths (pt_cnt has N entries; one spare slot is read)
+    {
+        int* cnt_pad = nullptr;
+        TRY(tmp.alloc(&cnt_pad, Nz + 1));
+        HIP_TRY(hipMemsetAsync(cnt_pad, 0, sizeof(int) * (Nz + 1), st));
+        if (N) HIP_TRY(hipMemcpyAsync(cnt_pad, L.pt_cnt, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
         need = cub_bytes;
-        if (N) HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, need, cnt_o, L.pt_cnt, iota, L.perm, N, 0, bits_n, st));
-        HIP_TRY(hipMemsetAsync(slots, 0, sizeof(int) * (L.n_slices + 1), st));
-        HIP_TRY(hipMemsetAsync(hits, 0, sizeof(long long) * (Nz + 1), st));
-        if (N) hipLaunchKernelGGL(k_lay_rank, dim3((N + 255) / 256), dim3(256), 0, st, N, L.perm, L.pt_cnt, L.rank, slots, hits);
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, cnt_pad, ipt_ofs, N + 1, st));
+    }
+    // sizes the host needs: padded ELL length, pair-list length, status
+    int h_flags[4] = {0, 0, 0, 0}, h_P = 0;
+    long long h_E = 0;
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_P, L.slice_base + L.n_slices, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_E, L.hit_ofs + N, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    switch (h_flags[0]) {
+        case LAY_OK: break;
+        case LAY_E_CAM: return fail(SATBA_E_ARG, "cam_ind out of range [0, %d)", M);
+        case LAY_E_PT: return fail(SATBA_E_ARG, "pts_ind out of range [0, %d)", N);
+        case LAY_E_ORDER: return fail(SATBA_E_ARG, "pts_ind must be non-decreasing (point-major order)");
+        default: return fail(SATBA_E_ARG, "cameras must ascend strictly inside a point (ba_params.py:142-147 order)");
+    }
+    p->unit_weights = h_flags[1] ? 0 : 1;
+    memcpy(&p->w_max, h_flags + 2, sizeof(double));  // largest |weight| (bound of the fixed-point camera sums)
+    if (!(p->w_max > 0.0)) p->w_max = 1.0;
+    L.P = h_P; L.E = h_E;
+    if ((long long)L.P >= (1ll << 31) - 128 || L.E >= (1ll << 31)) return fail(SATBA_E_ARG, "observation or pair lists exceed 2^31 entries per shard");
+    p->create_ms[1] = ms_since(t0);
+    // sliced ELL
+    const size_t Pz = (size_t)std::max(L.P, 1);
+    TRY(dev_alloc(p, &L.e_cam, Pz + 64)); TRY(dev_alloc(p, &L.e_obs, Pz + 64)); TRY(dev_alloc(p, &L.e_w, Pz + 64));
+    HIP_TRY(hipMemsetAsync(L.e_cam, 0xFF, sizeof(int) * (Pz + 64), st));
+    HIP_TRY(hipMemsetAsync(L.e_obs, 0, sizeof(double2) * (Pz + 64), st));
+    HIP_TRY(hipMemsetAsync(L.e_w, 0, sizeof(double) * (Pz + 64), st));
+    if (K) {
+        hipLaunchKernelGGL(k_lay_fill_ell, dim3(grid_for(K, 256, 8192)), dim3(256), 0, st, K, o_cam, L.pts_ind, o_obs, o_w, o_ofs, L.rank,
+                           L.slice_base, ipt_ofs, L.e_cam, L.e_obs, L.e_w, L.obs_pos, io_cam, io_pos, io_pt);
+        // camera-major lists: stable sort of the internal point-major list by camera
+        hipLaunchKernelGGL(k_lay_iota, dim3(grid_for(K, 256, 4096)), dim3(256), 0, st, K, io_iota);
         need = cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, slots, L.slice_base, L.n_slices + 1, st));
-        need = cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, hits, L.hit_ofs, N + 1, st));
-        // internal point-major CSR: exclusive sum of the sorted lengths (pt_cnt has N entries; one spare slot is read)
-        {
-            int* cnt_pad = nullptr;
-            TMP(cnt_pad, Nz + 1);
-            HIP_TRY(hipMemsetAsync(cnt_pad, 0, sizeof(int) * (Nz + 1), st));
-            if (N) HIP_TRY(hipMemcpyAsync(cnt_pad, L.pt_cnt, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
-            need = cub_bytes;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub, need, cnt_pad, ipt_ofs, N + 1, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, need, io_cam, cm_key, io_iota, cm_io, (int)K, 0, bits_m, st));
+        hipLaunchKernelGGL(k_lay_gather2, dim3(grid_for(K, 256, 8192)), dim3(256), 0, st, K, cm_io, io_pos, io_pt, L.cm_pos, L.cm_pt);
+    }
+    hipLaunchKernelGGL((k_lay_offsets<int>), dim3(grid_for(K + 1, 256, 4096)), dim3(256), 0, st, K, M, cm_key, L.cam_ofs);
+    HIP_TRY(hipGetLastError());
+    p->create_ms[2] = ms_since(t0);
+    // pair lists
+    {
+        // point-range chunks: 32 MB windows of the 128-byte point records and >= 256 entries per (pair, chunk) item on
+        // average are the measured optimum between gather locality and the fixed cost per item at 200 x 1M x 10M; few
+        // cameras: enough items to fill the chip (>= 8192 waves), at least 64 entries each
+        int C = 1;
+        if (L.n_pairs > 0 && L.E > 0) {
+            C = (int)std::max<long long>(1, ((long long)N * 8 * PV_STRIDE + (32ll << 20) - 1) / (32ll << 20));
+            // weighted / robust runs: an XCD works on one (camera, chunk) group at a time and gathers the records AND the row
+            // scales of the camera's points in the chunk -- one merged record per point since round 5, ~256 bytes of lines (rounds 3-4:
+            // record and scales apart, ~384); that set should sit in the XCD's 4 MB L2 with room to spare.  200 x 1M x 10M, LM it/s
+            // of the soft_l1 loop with the merged records: 4 chunks 465, 5: 467, 6: 462, 7: 458, 8: 452, 10: 437, 12: 425, 16: 399
+            // (round 4, separate arrays, pair kernel alone: 4 chunks 1.24 ms, 8: 1.02, 12: 1.04).  The unit-weight kernels use one
+            // item per pair and do not look at the chunks
+            C = (int)std::max<long long>(C, (K / std::max(M, 1) * 256 + 2800000 - 1) / 2800000);
+            C = (int)std::max<long long>(1, std::min<long long>(C, L.E / L.n_pairs / 256));
+            C = (int)std::max<long long>(C, std::min<long long>((8192 + L.n_pairs - 1) / L.n_pairs, std::max<long long>(1, L.E / L.n_pairs / 64)));
+            if (const char* cs = getenv("SATBA_SCHUR_CHUNKS")) C = std::max(1, atoi(cs));
+            C = std::min(C, 64);
+            C = std::min(C, std::max(N, 1));
+            while (C > 1 && L.n_pairs * (long long)(C + 1) > (1ll << 27)) --C;
         }
-        // sizes the host needs: padded ELL length, pair-list length, status
-        int h_flags[4] = {0, 0, 0, 0}, h_P = 0;
-        long long h_E = 0;
-        HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&h_P, L.slice_base + L.n_slices, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&h_E, L.hit_ofs + N, sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        switch (h_flags[0]) {
-            case LAY_OK: break;
-            case LAY_E_CAM: return fail(SATBA_E_ARG, "cam_ind out of range [0, %d)", M);
-            case LAY_E_PT: return fail(SATBA_E_ARG, "pts_ind out of range [0, %d)", N);
-            case LAY_E_ORDER: return fail(SATBA_E_ARG, "pts_ind must be non-decreasing (point-major order)");
-            default: return fail(SATBA_E_ARG, "cameras must ascend strictly inside a point (ba_params.py:142-147 order)");
+        L.C = C;
+        const size_t n_ofs = (size_t)std::max<long long>(L.n_pairs, 1) * (C + 1) + 1;
+        TRY(dev_alloc(p, &L.pair_ofs, n_ofs)); TRY(dev_alloc(p, &L.pair_ij, (size_t)std::max<long long>(L.n_pairs, 1)));
+        const size_t Ez = (size_t)std::max<long long>(L.E, 1);
+        TRY(dev_alloc(p, &L.pair_pts, Ez)); TRY(dev_alloc(p, &L.pair_pi, Ez)); TRY(dev_alloc(p, &L.pair_pj, Ez));
+        if (M > 1) hipLaunchKernelGGL(k_lay_pair_ij, dim3(M - 1), dim3(64), 0, st, M, L.pair_ij);
+        if (L.E > 0) {
+            int *hk = nullptr, *hq = nullptr, *hpi = nullptr, *hpj = nullptr, *hi = nullptr, *hk_s = nullptr, *hi_s = nullptr;
+            TRY(tmp.alloc(&hk, Ez)); TRY(tmp.alloc(&hq, Ez)); TRY(tmp.alloc(&hpi, Ez)); TRY(tmp.alloc(&hpj, Ez));
+            TRY(tmp.alloc(&hi, Ez)); TRY(tmp.alloc(&hk_s, Ez)); TRY(tmp.alloc(&hi_s, Ez));
+            hipLaunchKernelGGL(k_lay_hits, dim3((N + 255) / 256), dim3(256), 0, st, N, M, L.pt_cnt, L.slice_base, L.ipt_ofs, L.e_cam, L.hit_ofs, hk, hq, hpi, hpj);
+            hipLaunchKernelGGL(k_lay_iota, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, hi);
+            int bits_p = 1;
+            while ((1ll << bits_p) < L.n_pairs) ++bits_p;
+            size_t need2 = 0;
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need2, hk, hk_s, hi, hi_s, (int)L.E, 0, bits_p, st));
+            char* cub2 = nullptr;
+            TRY(tmp.alloc(&cub2, need2 + 16));
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub2, need2, hk, hk_s, hi, hi_s, (int)L.E, 0, bits_p, st));  // stable: points stay ascending
+            hipLaunchKernelGGL(k_lay_gather3, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, hi_s, hq, hpi, hpj, L.pair_pts, L.pair_pi, L.pair_pj);
+            hipLaunchKernelGGL(k_lay_offsets_pair, dim3(grid_for(L.E + 1, 256, 8192)), dim3(256), 0, st, L.E, (long long)(n_ofs - 1), hk_s, L.pair_pts,
+                               std::max(N, 1), C, L.pair_ofs);
+        } else {
+            HIP_TRY(hipMemsetAsync(L.pair_ofs, 0, sizeof(long long) * n_ofs, st));
         }
-        p->unit_weights = h_flags[1] ? 0 : 1;
-        memcpy(&p->w_max, h_flags + 2, sizeof(double));  // largest |weight| (bound of the fixed-point camera sums)
-        if (!(p->w_max > 0.0)) p->w_max = 1.0;
-        L.P = h_P; L.E = h_E;
-        if ((long long)L.P >= (1ll << 31) - 128 || L.E >= (1ll << 31)) return fail(SATBA_E_ARG, "observation or pair lists exceed 2^31 entries per shard");
-        p->create_ms[1] = ms_since(t0);
-        // sliced ELL
-        const size_t Pz = (size_t)std::max(L.P, 1);
-        TRY(dev_alloc(p, &L.e_cam, Pz + 64)); TRY(dev_alloc(p, &L.e_obs, Pz + 64)); TRY(dev_alloc(p, &L.e_w, Pz + 64));
-        HIP_TRY(hipMemsetAsync(L.e_cam, 0xFF, sizeof(int) * (Pz + 64), st));
-        HIP_TRY(hipMemsetAsync(L.e_obs, 0, sizeof(double2) * (Pz + 64), st));
-        HIP_TRY(hipMemsetAsync(L.e_w, 0, sizeof(double) * (Pz + 64), st));
-        if (K) {
-            hipLaunchKernelGGL(k_lay_fill_ell, dim3(grid_for(K, 256, 8192)), dim3(256), 0, st, K, o_cam, L.pts_ind, o_obs, o_w, o_ofs, L.rank,
-                               L.slice_base, ipt_ofs, L.e_cam, L.e_obs, L.e_w, L.obs_pos, io_cam, io_pos, io_pt);
-            // camera-major lists: stable sort of the internal point-major list by camera
-            hipLaunchKernelGGL(k_lay_iota, dim3(grid_for(K, 256, 4096)), dim3(256), 0, st, K, io_iota);
-            need = cub_bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, need, io_cam, cm_key, io_iota, cm_io, (int)K, 0, bits_m, st));
-            hipLaunchKernelGGL(k_lay_gather2, dim3(grid_for(K, 256, 8192)), dim3(256), 0, st, K, cm_io, io_pos, io_pt, L.cm_pos, L.cm_pt);
-        }
-        hipLaunchKernelGGL((k_lay_offsets<int>), dim3(grid_for(K + 1, 256, 4096)), dim3(256), 0, st, K, M, cm_key, L.cam_ofs);
         HIP_TRY(hipGetLastError());
-        p->create_ms[2] = ms_since(t0);
-        // pair lists
-        {
-            // point-range chunks: 32 MB windows of the 128-byte point records and >= 256 entries per (pair, chunk) item on
-            // average are the measured optimum between gather locality and the fixed cost per item at 200 x 1M x 10M; few
-            // cameras: enough items to fill the chip (>= 8192 waves), at least 64 entries each
-            int C = 1;
-            if (L.n_pairs > 0 && L.E > 0) {
-                C = (int)std::max<long long>(1, ((long long)N * 8 * PV_STRIDE + (32ll << 20) - 1) / (32ll << 20));
-                // weighted / robust runs: an XCD works on one (camera, chunk) group at a time and gathers the records AND the row
-                // scales of the camera's points in the chunk -- one merged record per point since round 5, ~256 bytes of lines (rounds 3-4:
-                // record and scales apart, ~384); that set should sit in the XCD's 4 MB L2 with room to spare.  200 x 1M x 10M, LM it/s
-                // of the soft_l1 loop with the merged records: 4 chunks 465, 5: 467, 6: 462, 7: 458, 8: 452, 10: 437, 12: 425, 16: 399
-                // (round 4, separate arrays, pair kernel alone: 4 chunks 1.24 ms, 8: 1.02, 12: 1.04).  The unit-weight kernels use one
-                // item per pair and do not look at the chunks
-                C = (int)std::max<long long>(C, (K / std::max(M, 1) * 256 + 2800000 - 1) / 2800000);
-                C = (int)std::max<long long>(1, std::min<long long>(C, L.E / L.n_pairs / 256));
-                C = (int)std::max<long long>(C, std::min<long long>((8192 + L.n_pairs - 1) / L.n_pairs, std::max<long long>(1, L.E / L.n_pairs / 64)));
-                if (const char* cs = getenv("SATBA_SCHUR_CHUNKS")) C = std::max(1, atoi(cs));
-                C = std::min(C, 64);
-                C = std::min(C, std::max(N, 1));
-                while (C > 1 && L.n_pairs * (long long)(C + 1) > (1ll << 27)) --C;
-            }
-            L.C = C;
-            const size_t n_ofs = (size_t)std::max<long long>(L.n_pairs, 1) * (C + 1) + 1;
-            TRY(dev_alloc(p, &L.pair_ofs, n_ofs)); TRY(dev_alloc(p, &L.pair_ij, (size_t)std::max<long long>(L.n_pairs, 1)));
-            const size_t Ez = (size_t)std::max<long long>(L.E, 1);
-            TRY(dev_alloc(p, &L.pair_pts, Ez)); TRY(dev_alloc(p, &L.pair_pi, Ez)); TRY(dev_alloc(p, &L.pair_pj, Ez));
-            if (M > 1) hipLaunchKernelGGL(k_lay_pair_ij, dim3(M - 1), dim3(64), 0, st, M, L.pair_ij);
-            if (L.E > 0) {
-                int *hk = nullptr, *hq = nullptr, *hpi = nullptr, *hpj = nullptr, *hi = nullptr, *hk_s = nullptr, *hi_s = nullptr;
-                TMP(hk, Ez); TMP(hq, Ez); TMP(hpi, Ez); TMP(hpj, Ez); TMP(hi, Ez); TMP(hk_s, Ez); TMP(hi_s, Ez);
-                hipLaunchKernelGGL(k_lay_hits, dim3((N + 255) / 256), dim3(256), 0, st, N, M, L.pt_cnt, L.slice_base, L.ipt_ofs, L.e_cam, L.hit_ofs, hk, hq, hpi, hpj);
-                hipLaunchKernelGGL(k_lay_iota, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, hi);
-                int bits_p = 1;
-                while ((1ll << bits_p) < L.n_pairs) ++bits_p;
-                size_t need2 = 0;
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need2, hk, hk_s, hi, hi_s, (int)L.E, 0, bits_p, st));
-                char* cub2 = nullptr;
-                TMP(cub2, need2 + 16);
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub2, need2, hk, hk_s, hi, hi_s, (int)L.E, 0, bits_p, st));  // stable: points stay ascending
-                hipLaunchKernelGGL(k_lay_gather3, dim3(grid_for(L.E, 256, 8192)), dim3(256), 0, st, L.E, hi_s, hq, hpi, hpj, L.pair_pts, L.pair_pi, L.pair_pj);
-                hipLaunchKernelGGL(k_lay_offsets_pair, dim3(grid_for(L.E + 1, 256, 8192)), dim3(256), 0, st, L.E, (long long)(n_ofs - 1), hk_s, L.pair_pts,
-                                   std::max(N, 1), C, L.pair_ofs);
-            } else {
-                HIP_TRY(hipMemsetAsync(L.pair_ofs, 0, sizeof(long long) * n_ofs, st));
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        {   // most observations of one camera (range of the fixed-point camera sums)
-            std::vector<int> h_ofs((size_t)M + 1);
-            HIP_TRY(hipMemcpyAsync(h_ofs.data(), L.cam_ofs, sizeof(int) * (M + 1), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            int mx = 1;
-            for (int c = 0; c < M; ++c) mx = std::max(mx, h_ofs[c + 1] - h_ofs[c]);
-            p->n_max_cam = (double)mx;
-        }
-        p->create_ms[3] = ms_since(t0);
-        return 0;
-    }();
-#undef TMP
-    free_tmp();
-    return rc;
+    }
+    {   // most observations of one camera (range of the fixed-point camera sums)
+        std::vector<int> h_ofs((size_t)M + 1);
+        HIP_TRY(hipMemcpyAsync(h_ofs.data(), L.cam_ofs, sizeof(int) * (M + 1), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int mx = 1;
+        for (int c = 0; c < M; ++c) mx = std::max(mx, h_ofs[c + 1] - h_ofs[c]);
+        p->n_max_cam = (double)mx;
+    }
+    p->create_ms[3] = ms_since(t0);
+    return 0;
 }
 
 extern "C" {
@@ -1542,21 +1527,16 @@ int satba_get_blocks(satba_problem* p, double* U, double* gc, double* V, double*
     if (U) {
         // the linearize kernel only keeps diag(U_c): form the full blocks with the camera-major pass (inspection only)
         double *dU = nullptr, *dg = nullptr;
-        HIP_TRY(hipMalloc((void**)&dU, sizeof(double) * nU));
-        HIP_TRY(hipMalloc((void**)&dg, sizeof(double) * p->n_c));
-        int rc = [&]() -> int {
-            if (!p->f_valid) {  // the default linearize kernel does not store the residuals: evaluate them for this view
-                TRY(launch_residual(p, false, p->d_f, p->d_scal));
-                p->f_valid = true;
-            }
-            TRY(launch_cam_sums(p, nullptr, dU, dg));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            HIP_TRY(hipMemcpy(U, dU, sizeof(double) * nU, hipMemcpyDeviceToHost));
-            return 0;
-        }();
-        (void)hipFree(dU);
-        (void)hipFree(dg);
-        if (rc) return rc;
+        DevAllocs tmp;
+        TRY(tmp.alloc(&dU, nU));
+        TRY(tmp.alloc(&dg, (size_t)p->n_c));
+        if (!p->f_valid) {  // the default linearize kernel does not store the residuals: evaluate them for this view
+            TRY(launch_residual(p, false, p->d_f, p->d_scal));
+            p->f_valid = true;
+        }
+        TRY(launch_cam_sums(p, nullptr, dU, dg));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        HIP_TRY(hipMemcpy(U, dU, sizeof(double) * nU, hipMemcpyDeviceToHost));
     }
     if (gc) HIP_TRY(hipMemcpy(gc, p->payload() + nU, sizeof(double) * p->n_c, hipMemcpyDeviceToHost));
     if (V) TRY(download_permuted(p, p->d_V, V, 0, 6));
@@ -1568,21 +1548,17 @@ int satba_get_jacobian(satba_problem* p, double* Jc, double* Jp) {
     if (!p || !Jc || !Jp) return fail(SATBA_E_ARG, "null argument");
     HIP_TRY(hipSetDevice(p->device));
     double *dJc = nullptr, *dJp = nullptr;
-    HIP_TRY(hipMalloc((void**)&dJc, sizeof(double) * (2 * p->K * p->NP + 1)));
-    HIP_TRY(hipMalloc((void**)&dJp, sizeof(double) * (6 * p->K + 1)));
+    DevAllocs tmp;
+    TRY(tmp.alloc(&dJc, (size_t)(2 * p->K * p->NP + 1)));
+    TRY(tmp.alloc(&dJp, (size_t)(6 * p->K + 1)));
     ObsArgs a = obs_args(p, false);
-    int rc = [&]() -> int {
-        SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jacobian<MODEL, NP>), dim3(grid_for(p->K, 256, 1024)), dim3(256), 0, p->stream, a, p->L.pts_ind,
-                                             p->L.rank, p->L.obs_pos, dJc, dJp));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipMemcpy(Jc, dJc, sizeof(double) * 2 * p->K * p->NP, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(Jp, dJp, sizeof(double) * 6 * p->K, hipMemcpyDeviceToHost));
-        return 0;
-    }();
-    (void)hipFree(dJc);
-    (void)hipFree(dJp);
-    return rc;
+    SATBA_DISPATCH(p, hipLaunchKernelGGL((k_jacobian<MODEL, NP>), dim3(grid_for(p->K, 256, 1024)), dim3(256), 0, p->stream, a, p->L.pts_ind,
+                                         p->L.rank, p->L.obs_pos, dJc, dJp));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipMemcpy(Jc, dJc, sizeof(double) * 2 * p->K * p->NP, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Jp, dJp, sizeof(double) * 6 * p->K, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int satba_get_exchange(satba_problem* p, int64_t offset, int64_t n, double* host_out) {

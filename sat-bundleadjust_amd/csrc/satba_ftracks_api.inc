@@ -5,6 +5,7 @@ struct satba_ftracks {
     int64_t n_tracks = 0, n_obs = 0;
     int *pt_ofs = nullptr, *cam_ind = nullptr, *kp_id = nullptr;
     double *obs = nullptr, *scale = nullptr;
+    DevAllocs mem;  // owns the arrays
 };
 
 extern "C++" {
@@ -22,12 +23,12 @@ void ft_pair_bits(int32_t n_cam, int32_t n_pairs, const int32_t* pairs, std::vec
 }
 
 template <class T>
-int ft_scan(TriScratch& s, void* d_tmp, size_t tmp_bytes, const T* in, T* out, size_t n) {
+int ft_scan(DevRun& s, void* d_tmp, size_t tmp_bytes, const T* in, T* out, size_t n) {
     HIP_TRY(rocprim::exclusive_scan(d_tmp, tmp_bytes, in, out, T(0), n, rocprim::plus<T>(), s.stream));
     return 0;
 }
 
-int ft_has_pair(TriScratch& s, int n_tr, int n_cam, int n_adj, const int* d_ofs, const int* d_cam, const unsigned* d_bits, long long n_words,
+int ft_has_pair(DevRun& s, int n_tr, int n_cam, int n_adj, const int* d_ofs, const int* d_cam, const unsigned* d_bits, long long n_words,
                 unsigned char* d_keep, int* d_group, int lds_optin) {
     if (!n_tr) return 0;
     const unsigned blocks = (unsigned)std::min<long long>(((long long)n_tr + FT_THREADS - 1) / FT_THREADS, 2048);
@@ -48,15 +49,13 @@ int ft_has_pair(TriScratch& s, int n_tr, int n_cam, int n_adj, const int* d_ofs,
 void ft_free(satba_ftracks* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    for (void* q : {(void*)t->pt_ofs, (void*)t->cam_ind, (void*)t->kp_id, (void*)t->obs, (void*)t->scale})
-        if (q) (void)hipFree(q);
     delete t;
 }
 
 int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, const float* kp, int64_t n_matches, const int32_t* matches,
              const std::vector<unsigned>& bits, int32_t n_adj, int64_t* counts, int32_t device, float* kernel_ms) {
     const int n_kp = ofs32[(size_t)n_cam], n = (int)n_matches;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     t->device = device;
     const dim3 blk(FT_THREADS);
@@ -68,16 +67,16 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
     unsigned* d_bits;
     TRY(s.upload(&d_kp_ofs, ofs32.data(), ofs32.size())); TRY(s.upload(&d_kp, kp, 3 * (size_t)n_kp));
     TRY(s.upload(&d_matches, matches, 4 * (size_t)n)); TRY(s.upload(&d_bits, bits.data(), bits.size()));
-    TRY(s.upload(&d_parent, (const int*)nullptr, (size_t)n_kp)); TRY(s.upload(&d_label, (const int*)nullptr, (size_t)n_kp));
-    TRY(s.upload(&d_cnt, (const int*)nullptr, (size_t)n_kp)); TRY(s.upload(&d_wkey, (const unsigned long long*)nullptr, (size_t)n_kp));
-    TRY(s.upload(&d_is_root, (const int*)nullptr, (size_t)n_kp + 1)); TRY(s.upload(&d_is_matched, (const int*)nullptr, (size_t)n_kp + 1));
-    TRY(s.upload(&d_track_of_root, (const int*)nullptr, (size_t)n_kp + 1)); TRY(s.upload(&d_pos, (const int*)nullptr, (size_t)n_kp + 1));
-    TRY(s.upload(&d_conf, (const int*)nullptr, 1));
+    TRY(s.alloc(&d_parent, (size_t)n_kp)); TRY(s.alloc(&d_label, (size_t)n_kp));
+    TRY(s.alloc(&d_cnt, (size_t)n_kp)); TRY(s.alloc(&d_wkey, (size_t)n_kp));
+    TRY(s.alloc(&d_is_root, (size_t)n_kp + 1)); TRY(s.alloc(&d_is_matched, (size_t)n_kp + 1));
+    TRY(s.alloc(&d_track_of_root, (size_t)n_kp + 1)); TRY(s.alloc(&d_pos, (size_t)n_kp + 1));
+    TRY(s.alloc(&d_conf, 1));
     HIP_TRY(hipMemsetAsync(d_conf, 0, sizeof(int), s.stream));
     size_t tmp_scan = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, d_is_root, d_track_of_root, 0, (size_t)n_kp + 1, rocprim::plus<int>(), s.stream));
     char* d_tmp_scan;
-    TRY(s.upload(&d_tmp_scan, (const char*)nullptr, tmp_scan + 16));
+    TRY(s.alloc(&d_tmp_scan, tmp_scan + 16));
 
     // ---- components (ft_utils.py:115-149)
     HIP_TRY(hipEventRecord(s.e0, s.stream));
@@ -105,14 +104,14 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
     if (n_tr) {
         unsigned long long *d_key_a, *d_key_b;
         int *d_id_a, *d_id_b, *d_head, *d_cell_pos, *d_cell_trk, *d_cell_cam, *d_cell_kp, *d_tr_ofs, *d_group, *d_slot, *d_new_trk, *d_new_len, *d_pt_ofs;
-        TRY(s.upload(&d_key_a, (const unsigned long long*)nullptr, (size_t)n_c)); TRY(s.upload(&d_key_b, (const unsigned long long*)nullptr, (size_t)n_c));
-        TRY(s.upload(&d_id_a, (const int*)nullptr, (size_t)n_c)); TRY(s.upload(&d_id_b, (const int*)nullptr, (size_t)n_c));
-        TRY(s.upload(&d_head, (const int*)nullptr, (size_t)n_c + 1)); TRY(s.upload(&d_cell_pos, (const int*)nullptr, (size_t)n_c + 1));
-        TRY(s.upload(&d_cell_trk, (const int*)nullptr, (size_t)n_c)); TRY(s.upload(&d_cell_cam, (const int*)nullptr, (size_t)n_c));
-        TRY(s.upload(&d_cell_kp, (const int*)nullptr, (size_t)n_c)); TRY(s.upload(&d_tr_ofs, (const int*)nullptr, (size_t)n_tr + 1));
-        TRY(s.upload(&d_group, (const int*)nullptr, 2 * (size_t)n_tr + 1)); TRY(s.upload(&d_slot, (const int*)nullptr, 2 * (size_t)n_tr + 1));
-        TRY(s.upload(&d_new_trk, (const int*)nullptr, (size_t)n_tr)); TRY(s.upload(&d_new_len, (const int*)nullptr, (size_t)n_tr + 1));
-        TRY(s.upload(&d_pt_ofs, (const int*)nullptr, (size_t)n_tr + 1));
+        TRY(s.alloc(&d_key_a, (size_t)n_c)); TRY(s.alloc(&d_key_b, (size_t)n_c));
+        TRY(s.alloc(&d_id_a, (size_t)n_c)); TRY(s.alloc(&d_id_b, (size_t)n_c));
+        TRY(s.alloc(&d_head, (size_t)n_c + 1)); TRY(s.alloc(&d_cell_pos, (size_t)n_c + 1));
+        TRY(s.alloc(&d_cell_trk, (size_t)n_c)); TRY(s.alloc(&d_cell_cam, (size_t)n_c));
+        TRY(s.alloc(&d_cell_kp, (size_t)n_c)); TRY(s.alloc(&d_tr_ofs, (size_t)n_tr + 1));
+        TRY(s.alloc(&d_group, 2 * (size_t)n_tr + 1)); TRY(s.alloc(&d_slot, 2 * (size_t)n_tr + 1));
+        TRY(s.alloc(&d_new_trk, (size_t)n_tr)); TRY(s.alloc(&d_new_len, (size_t)n_tr + 1));
+        TRY(s.alloc(&d_pt_ofs, (size_t)n_tr + 1));
         int key_bits = 1;
         while (key_bits < 64 && ((unsigned long long)n_tr * (unsigned long long)n_cam) >> key_bits) ++key_bits;
         size_t tmp_sort = 0, tmp_scan2 = 0;
@@ -120,7 +119,7 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
         HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan2, d_head, d_cell_pos, 0, (size_t)std::max(n_c, 2 * n_tr) + 1, rocprim::plus<int>(), s.stream));
         const size_t tmp_bytes = std::max(tmp_sort, tmp_scan2) + 16;
         char* d_tmp;
-        TRY(s.upload(&d_tmp, (const char*)nullptr, tmp_bytes));
+        TRY(s.alloc(&d_tmp, tmp_bytes));
 
         hipLaunchKernelGGL(k_ft_candidates, grid(n_kp), blk, 0, s.stream, n_kp, (int)n_cam, d_kp_ofs, d_label, d_track_of_root, d_is_matched, d_pos, d_key_a,
                            d_id_a);
@@ -136,7 +135,7 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
         HIP_TRY(hipGetLastError());
 
         // ---- baseline check and the fixed-first partition (ft_utils.py:38-62, ft_pipeline.py:175-179)
-        TRY(ft_has_pair(s, n_tr, n_cam, n_adj, d_tr_ofs, d_cell_cam, d_bits, (long long)bits.size(), nullptr, d_group, trk_lds_limit(device)));
+        TRY(ft_has_pair(s, n_tr, n_cam, n_adj, d_tr_ofs, d_cell_cam, d_bits, (long long)bits.size(), nullptr, d_group, dev_lds_limit(device)));
         TRY(ft_scan(s, d_tmp, tmp_bytes, d_group, d_slot, 2 * (size_t)n_tr + 1));
         HIP_TRY(hipMemsetAsync(d_new_len, 0, sizeof(int) * ((size_t)n_tr + 1), s.stream));
         hipLaunchKernelGGL(k_ft_lengths, grid(n_tr), blk, 0, s.stream, n_tr, d_tr_ofs, d_group, d_slot, d_new_trk, d_new_len);
@@ -152,11 +151,11 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
         HIP_TRY(hipStreamSynchronize(s.stream));
 
         // ---- the lists, in the handle's own memory
-        HIP_TRY(hipMalloc((void**)&t->pt_ofs, sizeof(int) * ((size_t)res[1] + 1)));
-        HIP_TRY(hipMalloc((void**)&t->cam_ind, sizeof(int) * (size_t)std::max(res[2], 1)));
-        HIP_TRY(hipMalloc((void**)&t->kp_id, sizeof(int) * (size_t)std::max(res[2], 1)));
-        HIP_TRY(hipMalloc((void**)&t->obs, sizeof(double) * 2 * (size_t)std::max(res[2], 1)));
-        HIP_TRY(hipMalloc((void**)&t->scale, sizeof(double) * (size_t)std::max(res[2], 1)));
+        TRY(t->mem.alloc(&t->pt_ofs, (size_t)res[1] + 1));
+        TRY(t->mem.alloc(&t->cam_ind, (size_t)std::max(res[2], 1)));
+        TRY(t->mem.alloc(&t->kp_id, (size_t)std::max(res[2], 1)));
+        TRY(t->mem.alloc(&t->obs, 2 * (size_t)std::max(res[2], 1)));
+        TRY(t->mem.alloc(&t->scale, (size_t)std::max(res[2], 1)));
         HIP_TRY(hipMemcpyAsync(t->pt_ofs, d_pt_ofs, sizeof(int) * ((size_t)res[1] + 1), hipMemcpyDeviceToDevice, s.stream));
         if (res[2]) {
             hipLaunchKernelGGL(k_ft_emit, grid(n_cells), blk, 0, s.stream, n_cells, d_cell_trk, d_cell_cam, d_cell_kp, d_tr_ofs, d_new_trk, d_pt_ofs,
@@ -164,7 +163,7 @@ int ft_build(satba_ftracks* t, int32_t n_cam, const std::vector<int>& ofs32, con
             HIP_TRY(hipGetLastError());
         }
     } else {
-        HIP_TRY(hipMalloc((void**)&t->pt_ofs, sizeof(int)));
+        TRY(t->mem.alloc(&t->pt_ofs, 1));
         HIP_TRY(hipMemsetAsync(t->pt_ofs, 0, sizeof(int), s.stream));
     }
     HIP_TRY(hipEventRecord(s.e1, s.stream));
@@ -238,14 +237,14 @@ int satba_tracks_have_pair(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, 
     if (!n_pts) return 0;
     std::vector<unsigned> bits;
     ft_pair_bits(n_cam, n_pairs, pairs, bits);
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     int *d_ofs, *d_cam;
     unsigned* d_bits;
     unsigned char* d_keep;
     TRY(s.upload(&d_ofs, ofs32.data(), ofs32.size())); TRY(s.upload(&d_cam, cam_ind, (size_t)pt_ofs[n_pts]));
-    TRY(s.upload(&d_bits, bits.data(), bits.size())); TRY(s.upload(&d_keep, (const unsigned char*)nullptr, (size_t)n_pts));
-    TRY(ft_has_pair(s, (int)n_pts, n_cam, 0, d_ofs, d_cam, d_bits, (long long)bits.size(), d_keep, nullptr, trk_lds_limit(device)));
+    TRY(s.upload(&d_bits, bits.data(), bits.size())); TRY(s.alloc(&d_keep, (size_t)n_pts));
+    TRY(ft_has_pair(s, (int)n_pts, n_cam, 0, d_ofs, d_cam, d_bits, (long long)bits.size(), d_keep, nullptr, dev_lds_limit(device)));
     HIP_TRY(hipMemcpyAsync(keep, d_keep, (size_t)n_pts, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(hipStreamSynchronize(s.stream));
     return 0;

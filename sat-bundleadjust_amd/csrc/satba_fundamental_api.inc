@@ -29,15 +29,15 @@ int satba_rpc_fundamental(int32_t n_cam, const double* tables, int32_t n_pairs, 
     const size_t np = (size_t)n_pairs, n3 = (size_t)n * n * n;
     std::vector<double> ranges(np * 6);
     for (size_t p = 0; p < np; ++p) fnd_ranges(roi + 4 * p, tables + (size_t)pairs[2 * p] * 90, n, ranges.data() + 6 * p);
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     FundamentalArgs a{};
     a.n = n;
     double *d_tab, *d_rg, *d_out;
     int *d_pairs, *d_status;
     TRY(s.upload(&d_tab, tables, (size_t)n_cam * 90)); TRY(s.upload(&d_rg, ranges.data(), ranges.size())); TRY(s.upload(&d_pairs, pairs, np * 2));
-    TRY(s.upload(&d_out, (const double*)nullptr, np * 9)); TRY(s.upload(&d_status, (const int*)nullptr, np));
-    if (matches) TRY(s.upload(&a.matches, (const double*)nullptr, np * n3 * 4));
+    TRY(s.alloc(&d_out, np * 9)); TRY(s.alloc(&d_status, np));
+    if (matches) TRY(s.alloc(&a.matches, np * n3 * 4));
     a.tables = d_tab; a.pairs = d_pairs; a.ranges = d_rg; a.F5 = d_out; a.sv = d_out + np * 5; a.status = d_status;
     HIP_TRY(hipEventRecord(s.e0, s.stream));
     hipLaunchKernelGGL(k_fundamental, dim3(n_pairs), dim3(FND_THREADS), sizeof(double) * 4 * n3, s.stream, a);

@@ -538,16 +538,12 @@ int satba_lm_scalars(int32_t device, int64_t n, const double* in, double* out) {
     }
     const size_t bytes = sizeof(double) * 6 * (size_t)n;
     double *d_in = nullptr, *d_out = nullptr;
-    const int rc = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&d_in, bytes));
-        HIP_TRY(hipMalloc((void**)&d_out, bytes));
-        HIP_TRY(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_lm_scalars, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t) nullptr, (long long)n, d_in, d_out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));  // (waits for the kernel: the default stream)
-        return 0;
-    }();
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevAllocs tmp;
+    TRY(tmp.alloc(&d_in, 6 * (size_t)n));
+    TRY(tmp.alloc(&d_out, 6 * (size_t)n));
+    HIP_TRY(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_lm_scalars, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t) nullptr, (long long)n, d_in, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));  // (waits for the kernel: the default stream)
+    return 0;
 }

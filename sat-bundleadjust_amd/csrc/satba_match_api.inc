@@ -6,6 +6,7 @@ struct satba_matches {
     int64_t n_matches = 0;
     std::vector<int64_t> pair_ofs;
     int *kp_i = nullptr, *kp_j = nullptr;
+    DevAllocs mem;  // owns the arrays
 };
 
 extern "C++" {
@@ -13,8 +14,6 @@ namespace {
 void mt_free(satba_matches* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    if (m->kp_i) (void)hipFree(m->kp_i);
-    if (m->kp_j) (void)hipFree(m->kp_j);
     delete m;
 }
 
@@ -72,7 +71,7 @@ int mt_run(satba_matches* m, int32_t n_cam, const int64_t* n_kp, const float* co
     for (int32_t p = 0; p < n_pairs; ++p)
         for (int t = 0; t < hp[(size_t)p].cap[0] / MT_TILE; ++t) slot_pair[(size_t)(hp[(size_t)p].ofs[0] / MT_TILE + t)] = p;
 
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     m->device = device;
     m->n_pairs = n_pairs;
@@ -80,19 +79,19 @@ int mt_run(satba_matches* m, int32_t n_cam, const int64_t* n_kp, const float* co
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     float* d_feat; double2* d_utm; signed char* d_rec; int *d_nrm, *d_flag, *d_sel, *d_nrm_s, *d_slot_pair, *d_hit, *d_pos, *d_kpj;
     float2* d_xy; float* d_xx_s; MatchPair* d_pairs;
-    TRY(s.upload(&d_feat, (const float*)nullptr, (size_t)n_rows * MT_ROW)); TRY(s.upload(&d_utm, (const double2*)nullptr, (size_t)n_rows));
+    TRY(s.alloc(&d_feat, (size_t)n_rows * MT_ROW)); TRY(s.alloc(&d_utm, (size_t)n_rows));
     for (int32_t c = 0; c < n_cam; ++c) {
         if (!used[(size_t)c] || !n_kp[c]) continue;
         HIP_TRY(hipMemcpyAsync(d_feat + row0[(size_t)c] * MT_ROW, features[c], sizeof(float) * MT_ROW * (size_t)n_kp[c], hipMemcpyHostToDevice, s.stream));
         HIP_TRY(hipMemcpyAsync(d_utm + row0[(size_t)c], utm[c], sizeof(double2) * (size_t)n_kp[c], hipMemcpyHostToDevice, s.stream));
     }
-    TRY(s.upload(&d_rec, (const signed char*)nullptr, (size_t)n_rows * MT_DESC)); TRY(s.upload(&d_nrm, (const int*)nullptr, (size_t)n_rows));
-    TRY(s.upload(&d_xy, (const float2*)nullptr, (size_t)n_rows)); TRY(s.upload(&d_flag, (const int*)nullptr, 1));
-    TRY(s.upload(&d_sel, (const int*)nullptr, (size_t)n_slots)); TRY(s.upload(&d_nrm_s, (const int*)nullptr, (size_t)n_slots));
-    TRY(s.upload(&d_xx_s, (const float*)nullptr, (size_t)n_slots)); TRY(s.upload(&d_pairs, hp.data(), hp.size()));
+    TRY(s.alloc(&d_rec, (size_t)n_rows * MT_DESC)); TRY(s.alloc(&d_nrm, (size_t)n_rows));
+    TRY(s.alloc(&d_xy, (size_t)n_rows)); TRY(s.alloc(&d_flag, 1));
+    TRY(s.alloc(&d_sel, (size_t)n_slots)); TRY(s.alloc(&d_nrm_s, (size_t)n_slots));
+    TRY(s.alloc(&d_xx_s, (size_t)n_slots)); TRY(s.upload(&d_pairs, hp.data(), hp.size()));
     TRY(s.upload(&d_slot_pair, slot_pair.data(), slot_pair.size()));
-    TRY(s.upload(&d_hit, (const int*)nullptr, (size_t)n_slots + 1)); TRY(s.upload(&d_pos, (const int*)nullptr, (size_t)n_slots + 1));
-    TRY(s.upload(&d_kpj, (const int*)nullptr, (size_t)n_slots + 1));
+    TRY(s.alloc(&d_hit, (size_t)n_slots + 1)); TRY(s.alloc(&d_pos, (size_t)n_slots + 1));
+    TRY(s.alloc(&d_kpj, (size_t)n_slots + 1));
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), s.stream));
     if (n_slots) {  // slots past a side's selection are read (and masked) by the match kernels
         HIP_TRY(hipMemsetAsync(d_sel, 0, sizeof(int) * (size_t)n_slots, s.stream));
@@ -128,12 +127,12 @@ int mt_run(satba_matches* m, int32_t n_cam, const int64_t* n_kp, const float* co
     if (items.size() >= (size_t)1 << 31) return fail(SATBA_E_ARG, "too many work items: raise SATBA_MATCH_CHUNK");
     const int n_items = (int)items.size();
     MatchItem* d_items; MatchPart* d_part;
-    TRY(s.upload(&d_items, items.data(), items.size())); TRY(s.upload(&d_part, (const MatchPart*)nullptr, (size_t)n_part));
+    TRY(s.upload(&d_items, items.data(), items.size())); TRY(s.alloc(&d_part, (size_t)n_part));
     if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, s.stream));
     size_t tmp_scan = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, d_hit, d_pos, 0, (size_t)n_slots + 1, rocprim::plus<int>(), s.stream));
     char* d_tmp;
-    TRY(s.upload(&d_tmp, (const char*)nullptr, tmp_scan + 16));
+    TRY(s.alloc(&d_tmp, tmp_scan + 16));
     if (n_items) {
         if (float_path) {
             if (gate) hipLaunchKernelGGL(k_match_f32<true>, dim3((unsigned)n_items), dim3(MT_WQ), 0, s.stream, n_items, d_items, d_pairs, d_feat, d_sel, d_xx_s, chunk, epi_thr, d_part);
@@ -156,8 +155,8 @@ int mt_run(satba_matches* m, int32_t n_cam, const int64_t* n_kp, const float* co
         for (int32_t p = 0; p < n_pairs; ++p)
             HIP_TRY(hipMemcpyAsync(&h_pos[(size_t)p], d_pos + hp[(size_t)p].ofs[0], sizeof(int), hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipStreamSynchronize(s.stream));
-        HIP_TRY(hipMalloc((void**)&m->kp_i, sizeof(int) * (size_t)std::max(total, 1)));
-        HIP_TRY(hipMalloc((void**)&m->kp_j, sizeof(int) * (size_t)std::max(total, 1)));
+        TRY(m->mem.alloc(&m->kp_i, (size_t)std::max(total, 1)));
+        TRY(m->mem.alloc(&m->kp_j, (size_t)std::max(total, 1)));
         if (total) {
             hipLaunchKernelGGL(k_match_emit, grid, blk, 0, s.stream, n_slots, d_pairs, d_slot_pair, d_sel, d_hit, d_pos, d_kpj, m->kp_i, m->kp_j);
             HIP_TRY(hipGetLastError());

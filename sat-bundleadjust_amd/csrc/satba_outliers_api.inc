@@ -11,49 +11,44 @@ int satba_outliers(satba_problem* p, const double* err, double predef_thr, doubl
     double2* d_f = nullptr;
     unsigned char* d_rm = nullptr;
     unsigned long long* d_cnt = nullptr;
-    void* d_cub = nullptr;
-    std::vector<void*> tmp;
-    auto alloc = [&](void** q, size_t bytes) -> int { HIP_TRY(hipMalloc(q, bytes ? bytes : 1)); tmp.push_back(*q); return 0; };
-    int rc = [&]() -> int {
-        TRY(alloc((void**)&d_err, sizeof(double) * Pz)); TRY(alloc((void**)&d_cm, sizeof(double) * Kz)); TRY(alloc((void**)&d_sorted, sizeof(double) * Kz));
-        TRY(alloc((void**)&d_thr, sizeof(double) * p->M)); TRY(alloc((void**)&d_rm, Kz)); TRY(alloc((void**)&d_cnt, sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), p->stream));
-        HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(double) * Pz, p->stream));
-        if (err) {
-            TRY(alloc((void**)&d_in, sizeof(double) * Kz));
-            if (K) HIP_TRY(hipMemcpyAsync(d_in, err, sizeof(double) * K, hipMemcpyHostToDevice, p->stream));
-            if (K) hipLaunchKernelGGL(k_out_scatter_ell, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.obs_pos, d_in, d_err);
-        } else {
-            // reprojection errors at the current x: linear-loss residuals, whatever loss the handle is configured for
-            TRY(alloc((void**)&d_f, sizeof(double2) * Pz));
-            const int loss = p->loss;
-            p->loss = 0;
-            int r2 = launch_residual(p, false, d_f, p->d_scal);
-            p->loss = loss;
-            if (r2) return r2;
-            hipLaunchKernelGGL(k_out_err_ell, dim3(grid_for(L.P, 256, 4096)), dim3(256), 0, p->stream, L.P, L.e_cam, d_f, L.e_w, d_err);
-        }
-        if (K) hipLaunchKernelGGL(k_out_gather_cm, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.cm_pos, d_err, d_cm);
-        HIP_TRY(hipGetLastError());
-        if (predef_thr < 0.0 && K) {  // ascending errors of every camera
-            size_t need = 0;
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, need, d_cm, d_sorted, (int)K, p->M, L.cam_ofs, L.cam_ofs + 1, 0, 64, p->stream));
-            TRY(alloc(&d_cub, need + 16));
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(d_cub, need, d_cm, d_sorted, (int)K, p->M, L.cam_ofs, L.cam_ofs + 1, 0, 64, p->stream));
-        }
-        hipLaunchKernelGGL(k_out_elbow, dim3(p->M), dim3(256), 0, p->stream, L.cam_ofs, d_sorted, predef_thr, min_thr, d_thr);
-        if (K) hipLaunchKernelGGL(k_out_mask, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.obs_pos, L.e_cam, d_err, d_thr, d_rm, d_cnt);
-        HIP_TRY(hipGetLastError());
-        unsigned long long cnt = 0;
-        HIP_TRY(hipMemcpyAsync(cam_thr, d_thr, sizeof(double) * p->M, hipMemcpyDeviceToHost, p->stream));
-        if (K) HIP_TRY(hipMemcpyAsync(remove, d_rm, (size_t)K, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        *n_removed = (int64_t)cnt;
-        return 0;
-    }();
-    for (void* q : tmp) (void)hipFree(q);
-    return rc;
+    char* d_cub = nullptr;
+    DevAllocs tmp;
+    TRY(tmp.alloc(&d_err, Pz)); TRY(tmp.alloc(&d_cm, Kz)); TRY(tmp.alloc(&d_sorted, Kz));
+    TRY(tmp.alloc(&d_thr, (size_t)p->M)); TRY(tmp.alloc(&d_rm, Kz)); TRY(tmp.alloc(&d_cnt, 1));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), p->stream));
+    HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(double) * Pz, p->stream));
+    if (err) {
+        TRY(tmp.alloc(&d_in, Kz));
+        if (K) HIP_TRY(hipMemcpyAsync(d_in, err, sizeof(double) * K, hipMemcpyHostToDevice, p->stream));
+        if (K) hipLaunchKernelGGL(k_out_scatter_ell, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.obs_pos, d_in, d_err);
+    } else {
+        // reprojection errors at the current x: linear-loss residuals, whatever loss the handle is configured for
+        TRY(tmp.alloc(&d_f, Pz));
+        const int loss = p->loss;
+        p->loss = 0;
+        int r2 = launch_residual(p, false, d_f, p->d_scal);
+        p->loss = loss;
+        if (r2) return r2;
+        hipLaunchKernelGGL(k_out_err_ell, dim3(grid_for(L.P, 256, 4096)), dim3(256), 0, p->stream, L.P, L.e_cam, d_f, L.e_w, d_err);
+    }
+    if (K) hipLaunchKernelGGL(k_out_gather_cm, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.cm_pos, d_err, d_cm);
+    HIP_TRY(hipGetLastError());
+    if (predef_thr < 0.0 && K) {  // ascending errors of every camera
+        size_t need = 0;
+        HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, need, d_cm, d_sorted, (int)K, p->M, L.cam_ofs, L.cam_ofs + 1, 0, 64, p->stream));
+        TRY(tmp.alloc(&d_cub, need + 16));
+        HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(d_cub, need, d_cm, d_sorted, (int)K, p->M, L.cam_ofs, L.cam_ofs + 1, 0, 64, p->stream));
+    }
+    hipLaunchKernelGGL(k_out_elbow, dim3(p->M), dim3(256), 0, p->stream, L.cam_ofs, d_sorted, predef_thr, min_thr, d_thr);
+    if (K) hipLaunchKernelGGL(k_out_mask, dim3(grid_for(K, 256, 4096)), dim3(256), 0, p->stream, K, L.obs_pos, L.e_cam, d_err, d_thr, d_rm, d_cnt);
+    HIP_TRY(hipGetLastError());
+    unsigned long long cnt = 0;
+    HIP_TRY(hipMemcpyAsync(cam_thr, d_thr, sizeof(double) * p->M, hipMemcpyDeviceToHost, p->stream));
+    if (K) HIP_TRY(hipMemcpyAsync(remove, d_rm, (size_t)K, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    *n_removed = (int64_t)cnt;
+    return 0;
 }
 
 // satba_reprojection_errors (include/satba.h): err_k = | |f_k / w_k| |_2 of the linear-loss residual pair at the current x, caller's

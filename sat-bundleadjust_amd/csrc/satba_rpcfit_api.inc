@@ -2,16 +2,16 @@
 int satba_rpc_fit(int32_t n_cam, int32_t n_samples, const double* target, const double* locs, double h, double tol, int32_t max_iter,
                   double* tables, double* rmse, int32_t* iters, int32_t device) {
     if (n_cam < 0 || n_samples < FIT_N || !target || !locs || !tables || max_iter < 0) return fail(SATBA_E_ARG, "bad argument (at least %d samples)", FIT_N);
-    for (size_t i = 0; i < (size_t)n_cam * n_samples * 2; ++i) if (!std::isfinite(target[i])) return fail(SATBA_E_NONFINITE, "non-finite target");
-    for (size_t i = 0; i < (size_t)n_cam * n_samples * 3; ++i) if (!std::isfinite(locs[i])) return fail(SATBA_E_NONFINITE, "non-finite location");
+    if (!cam_all_finite(target, (size_t)n_cam * n_samples * 2)) return fail(SATBA_E_NONFINITE, "non-finite target");
+    if (!cam_all_finite(locs, (size_t)n_cam * n_samples * 3)) return fail(SATBA_E_NONFINITE, "non-finite location");
     if (n_cam == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     double *d_t, *d_l, *d_tab, *d_rmse;
     int* d_it;
     TRY(s.upload(&d_t, target, (size_t)n_cam * n_samples * 2)); TRY(s.upload(&d_l, locs, (size_t)n_cam * n_samples * 3));
-    TRY(s.upload(&d_tab, (const double*)nullptr, (size_t)n_cam * 90)); TRY(s.upload(&d_rmse, (const double*)nullptr, (size_t)n_cam));
-    TRY(s.upload(&d_it, (const int*)nullptr, (size_t)n_cam));
+    TRY(s.alloc(&d_tab, (size_t)n_cam * 90)); TRY(s.alloc(&d_rmse, (size_t)n_cam));
+    TRY(s.alloc(&d_it, (size_t)n_cam));
     hipLaunchKernelGGL(k_rpc_fit, dim3(n_cam), dim3(FIT_THREADS), 0, s.stream, n_samples, d_t, d_l, h, tol, max_iter, d_tab, d_rmse, d_it);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(tables, d_tab, sizeof(double) * 90 * n_cam, hipMemcpyDeviceToHost, s.stream));
@@ -25,11 +25,11 @@ int satba_rpc_localization(const double* table, int64_t n, const double* col, co
                            int32_t device) {
     if (!table || n < 0 || (n && (!col || !row || !alt || !lon || !lat))) return fail(SATBA_E_ARG, "null argument");
     if (n == 0) return 0;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     double *d_tab, *d_c, *d_r, *d_a, *d_lo, *d_la;
     TRY(s.upload(&d_tab, table, (size_t)90)); TRY(s.upload(&d_c, col, (size_t)n)); TRY(s.upload(&d_r, row, (size_t)n)); TRY(s.upload(&d_a, alt, (size_t)n));
-    TRY(s.upload(&d_lo, (const double*)nullptr, (size_t)n)); TRY(s.upload(&d_la, (const double*)nullptr, (size_t)n));
+    TRY(s.alloc(&d_lo, (size_t)n)); TRY(s.alloc(&d_la, (size_t)n));
     hipLaunchKernelGGL(k_rpc_localize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, (long long)n, d_tab, d_c, d_r, d_a, d_lo, d_la);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(lon, d_lo, sizeof(double) * n, hipMemcpyDeviceToHost, s.stream));
@@ -45,7 +45,7 @@ int satba_rpc_refit(int32_t n_cam, const double* tables_in, const double* rt, co
     if (n_samples < 4 || n_samples > REFIT_MAX_N) return fail(SATBA_E_ARG, "n_samples must be in [4, %d]", REFIT_MAX_N);
     if (n_cam == 0) return 0;
     const int n3 = n_samples * n_samples * n_samples;
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     std::vector<RefitCam> cams((size_t)n_cam);
     for (int c = 0; c < n_cam; ++c) {
@@ -60,10 +60,10 @@ int satba_rpc_refit(int32_t n_cam, const double* tables_in, const double* rt, co
     RefitCam* d_cams;
     double *d_gt, *d_grid, *d_locs, *d_target, *d_tab, *d_err;
     int* d_cov;
-    TRY(s.upload(&d_cams, (const RefitCam*)nullptr, (size_t)n_cam)); TRY(s.upload(&d_gt, global_transform ? global_transform : zero3, (size_t)3));
-    TRY(s.upload(&d_grid, (const double*)nullptr, (size_t)n_cam * n3 * 3)); TRY(s.upload(&d_locs, (const double*)nullptr, (size_t)n_cam * n3 * 3));
-    TRY(s.upload(&d_target, (const double*)nullptr, (size_t)n_cam * n3 * 2)); TRY(s.upload(&d_tab, (const double*)nullptr, (size_t)n_cam * 90));
-    TRY(s.upload(&d_err, (const double*)nullptr, (size_t)n_cam * n3)); TRY(s.upload(&d_cov, (const int*)nullptr, (size_t)n_cam));
+    TRY(s.alloc(&d_cams, (size_t)n_cam)); TRY(s.upload(&d_gt, global_transform ? global_transform : zero3, (size_t)3));
+    TRY(s.alloc(&d_grid, (size_t)n_cam * n3 * 3)); TRY(s.alloc(&d_locs, (size_t)n_cam * n3 * 3));
+    TRY(s.alloc(&d_target, (size_t)n_cam * n3 * 2)); TRY(s.alloc(&d_tab, (size_t)n_cam * 90));
+    TRY(s.alloc(&d_err, (size_t)n_cam * n3)); TRY(s.alloc(&d_cov, (size_t)n_cam));
     std::vector<int> todo((size_t)n_cam), cov((size_t)n_cam);
     for (int c = 0; c < n_cam; ++c) todo[c] = c;
     std::vector<RefitCam> batch;

@@ -7,6 +7,7 @@ struct satba_sift {
     float* planes = nullptr;  // every Gaussian plane, when keep_planes
     SiftGeom geom;
     std::vector<size_t> oct_ofs;
+    DevAllocs mem;  // owns rows and planes
 };
 
 extern "C++" {
@@ -14,8 +15,6 @@ namespace {
 void sf_free(satba_sift* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    if (s->rows) (void)hipFree(s->rows);
-    if (s->planes) (void)hipFree(s->planes);
     delete s;
 }
 
@@ -39,19 +38,21 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
     for (int o = 0; o < n_oct; ++o) S->oct_ofs[(size_t)o + 1] = S->oct_ofs[(size_t)o] + (size_t)n_planes * (size_t)G.w[o] * (size_t)G.h[o];
     const size_t n_plane0 = (size_t)G.w[0] * (size_t)G.h[0];
 
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     S->device = device;
     float *d_img, *d_tmp;
     unsigned* d_cnt;  // [0] max |pixel| bits, [1] candidates, [2] survivors of the interpolation, [3] survivors of the border test
     double* d_scale;
-    HIP_TRY(hipMalloc((void**)&S->planes, sizeof(float) * std::max<size_t>(S->oct_ofs[(size_t)n_oct], 1)));
-    TRY(s.upload(&d_img, (const float*)nullptr, (size_t)width * (size_t)height));
+    float* d_planes;  // the handle's when it keeps them, of this run otherwise
+    TRY((keep_planes ? S->mem : s).alloc(&d_planes, S->oct_ofs[(size_t)n_oct]));
+    if (keep_planes) S->planes = d_planes;
+    TRY(s.alloc(&d_img, (size_t)width * (size_t)height));
     HIP_TRY(hipMemcpy2DAsync(d_img, sizeof(float) * (size_t)width, image, sizeof(float) * (size_t)row_stride, sizeof(float) * (size_t)width, (size_t)height,
                              hipMemcpyHostToDevice, s.stream));
-    TRY(s.upload(&d_tmp, (const float*)nullptr, n_plane0));
-    TRY(s.upload(&d_cnt, (const unsigned*)nullptr, 4));
-    TRY(s.upload(&d_scale, (const double*)nullptr, 1));
+    TRY(s.alloc(&d_tmp, n_plane0));
+    TRY(s.alloc(&d_cnt, 4));
+    TRY(s.alloc(&d_scale, 1));
     HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned) * 4, s.stream));
 
     SiftPlanes P;
@@ -60,7 +61,7 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
     P.thr = G.thr;
     P.sigma_ratio = G.sigma[0][1] / G.sigma[0][0];
     for (int o = 0; o < n_oct; ++o) {
-        P.base[o] = S->planes + S->oct_ofs[(size_t)o];
+        P.base[o] = d_planes + S->oct_ofs[(size_t)o];
         P.w[o] = G.w[o]; P.h[o] = G.h[o]; P.delta[o] = G.delta[o];
         for (int k = 0; k < n_planes; ++k) P.sigma[o][k] = G.sigma[o][k];
     }
@@ -87,7 +88,7 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
 
     // the Gaussian planes: the seed is in d_tmp; a blur reads `in`, writes its column pass to d_col and the result to `out`
     float* d_col;
-    TRY(s.upload(&d_col, (const float*)nullptr, n_plane0));
+    TRY(s.alloc(&d_col, n_plane0));
     for (int o = 0; o < n_oct; ++o) {
         const int w = G.w[o], h = G.h[o];
         const size_t plane = (size_t)w * (size_t)h;
@@ -108,7 +109,7 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
     unsigned n_cand = 0;
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
     for (int pass = 0; pass < 2; ++pass) {
-        TRY(s.upload(&d_keys, (const unsigned long long*)nullptr, cap));
+        TRY(s.alloc(&d_keys, cap));
         HIP_TRY(hipMemsetAsync(d_cnt + 1, 0, sizeof(unsigned), s.stream));
         for (int o = 0; o < n_oct; ++o) {
             const long long n_in = (long long)(G.w[o] - 2) * (long long)(G.h[o] - 2);
@@ -129,17 +130,17 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
     int total = 0;
     if (n) {
         // the reference's list order: (octave, scale, row, column) is the key itself
-        TRY(s.upload(&d_sorted, (const unsigned long long*)nullptr, (size_t)n));
+        TRY(s.alloc(&d_sorted, (size_t)n));
         size_t tmp_sort = 0, tmp_scan = 0;
         int *d_nori, *d_ofs;
         float* d_theta;
         SiftKey* d_cand;
         char* d_work;
-        TRY(s.upload(&d_nori, (const int*)nullptr, (size_t)n + 1)); TRY(s.upload(&d_ofs, (const int*)nullptr, (size_t)n + 1));
-        TRY(s.upload(&d_theta, (const float*)nullptr, (size_t)n * SIFT_MAX_ORI)); TRY(s.upload(&d_cand, (const SiftKey*)nullptr, (size_t)n));
+        TRY(s.alloc(&d_nori, (size_t)n + 1)); TRY(s.alloc(&d_ofs, (size_t)n + 1));
+        TRY(s.alloc(&d_theta, (size_t)n * SIFT_MAX_ORI)); TRY(s.alloc(&d_cand, (size_t)n));
         HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, d_keys, d_sorted, (size_t)n, 0, 64, s.stream));
         HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, d_nori, d_ofs, 0, (size_t)n + 1, rocprim::plus<int>(), s.stream));
-        TRY(s.upload(&d_work, (const char*)nullptr, std::max(tmp_sort, tmp_scan) + 16));
+        TRY(s.alloc(&d_work, std::max(tmp_sort, tmp_scan) + 16));
         HIP_TRY(rocprim::radix_sort_keys(d_work, tmp_sort, d_keys, d_sorted, (size_t)n, 0, 64, s.stream));
         hipLaunchKernelGGL(k_sift_refine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, P, (const unsigned long long*)d_sorted, n, d_cand, d_cnt + 2);
         HIP_TRY(hipMemsetAsync(d_nori + n, 0, sizeof(int), s.stream));
@@ -152,7 +153,7 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
         HIP_TRY(hipStreamSynchronize(s.stream));
         counts[3] = stage[0];
         counts[4] = stage[1];
-        HIP_TRY(hipMalloc((void**)&S->rows, sizeof(float) * SIFT_ROW * (size_t)std::max(total, 1)));
+        TRY(S->mem.alloc(&S->rows, SIFT_ROW * (size_t)std::max(total, 1)));
         if (total) {
             hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n), dim3(64), 0, s.stream, P, (const SiftKey*)d_cand, n, (const double*)d_scale, (const int*)d_nori,
                                (const int*)d_ofs, (const float*)d_theta, S->rows);
@@ -164,10 +165,6 @@ int sf_run(satba_sift* S, const float* image, int32_t width, int32_t height, int
     if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, s.e0, s.e1));
     S->n_rows = total;
     counts[0] = total;
-    if (!keep_planes) {
-        (void)hipFree(S->planes);
-        S->planes = nullptr;
-    }
     return 0;
 }
 }  // namespace

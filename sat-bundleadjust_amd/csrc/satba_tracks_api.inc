@@ -7,16 +7,9 @@ namespace {
 // 32 bits; cam_cnt (may be null): observations per camera
 int trk_check_lists(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, const int32_t* cam_ind, std::vector<int>& ofs32, std::vector<int>* cam_cnt) {
     if (n_cam <= 0 || n_pts < 0 || !pt_ofs) return fail(SATBA_E_ARG, "null or negative argument");
-    const int64_t K = pt_ofs[n_pts];
-    if (pt_ofs[0] != 0 || K < 0 || K >= (int64_t)1 << 31 || n_pts >= (int64_t)1 << 31) return fail(SATBA_E_ARG, "offsets out of range");
     if (n_cam >= 46341) return fail(SATBA_E_ARG, "the pair table holds fewer than 46 341 cameras");
-    if (K && !cam_ind) return fail(SATBA_E_ARG, "null observations");
-    ofs32.resize((size_t)n_pts + 1);
+    TRY(dev_check_offsets(n_pts, pt_ofs, cam_ind != nullptr, ofs32));
     if (cam_cnt) cam_cnt->assign((size_t)n_cam, 0);
-    for (int64_t i = 0; i <= n_pts; ++i) {
-        if (i && pt_ofs[i] < pt_ofs[i - 1]) return fail(SATBA_E_ARG, "pt_ofs must not decrease");
-        ofs32[(size_t)i] = (int)pt_ofs[i];
-    }
     for (int64_t i = 0; i < n_pts; ++i)
         for (int64_t o = pt_ofs[i]; o < pt_ofs[i + 1]; ++o) {
             if (cam_ind[o] < 0 || cam_ind[o] >= n_cam) return fail(SATBA_E_ARG, "camera index %d out of range", cam_ind[o]);
@@ -27,7 +20,7 @@ int trk_check_lists(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, const i
 }
 
 // pair counts of the live tracks into the packed triangle d_tri (zeroed here)
-int trk_connect(TriScratch& s, int N, int M, const int* d_ofs, const int* d_cam, const int* d_alive, int alive_is_mask, int* d_tri, int lds_optin) {
+int trk_connect(DevRun& s, int N, int M, const int* d_ofs, const int* d_cam, const int* d_alive, int alive_is_mask, int* d_tri, int lds_optin) {
     const size_t tri_bytes = sizeof(int) * (size_t)std::max(M * (M - 1) / 2, 1);
     HIP_TRY(hipMemsetAsync(d_tri, 0, tri_bytes, s.stream));
     if (!N || M < 2) return 0;
@@ -41,15 +34,6 @@ int trk_connect(TriScratch& s, int N, int M, const int* d_ofs, const int* d_cam,
     }
     HIP_TRY(hipGetLastError());
     return 0;
-}
-
-// LDS a workgroup may ask for (asked, not assumed: the Makefile's ARCH can be overridden)
-int trk_lds_limit(int device) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return 0;
-    int lim = (int)std::max(prop.sharedMemPerBlockOptin, prop.sharedMemPerBlock);
-    if (strstr(prop.gcnArchName, "gfx950")) lim = std::max(lim, 160 * 1024);  // CDNA4: 160 KB per workgroup
-    return lim;
 }
 
 // priority: up to three of 0 length, 1 scale, 2 cost (-1: unused); the missing ones follow in that order (numpy's rule for `order=`)
@@ -74,22 +58,17 @@ int trk_priority(const int32_t* priority, int out[3]) {
 int satba_track_keys(int64_t n_pts, const int64_t* pt_ofs, const double* scale, const double* err, int32_t* length, double* key_scale,
                      double* key_cost, int32_t device) {
     if (n_pts < 0 || !pt_ofs || (n_pts && (!length || !key_scale || !key_cost))) return fail(SATBA_E_ARG, "null or negative argument");
+    std::vector<int> ofs32;
+    TRY(dev_check_offsets(n_pts, pt_ofs, scale != nullptr, ofs32));
     const int64_t K = pt_ofs[n_pts];
-    if (pt_ofs[0] != 0 || K < 0 || K >= (int64_t)1 << 31 || n_pts >= (int64_t)1 << 31) return fail(SATBA_E_ARG, "offsets out of range");
-    if (K && !scale) return fail(SATBA_E_ARG, "null observations");
-    std::vector<int> ofs32((size_t)n_pts + 1);
-    for (int64_t i = 0; i <= n_pts; ++i) {
-        if (i && pt_ofs[i] < pt_ofs[i - 1]) return fail(SATBA_E_ARG, "pt_ofs must not decrease");
-        ofs32[(size_t)i] = (int)pt_ofs[i];
-    }
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     int *d_ofs, *d_len;
     double *d_scale, *d_err = nullptr, *d_ks, *d_kc;
     TRY(s.upload(&d_ofs, ofs32.data(), ofs32.size())); TRY(s.upload(&d_scale, scale, (size_t)K));
     if (err) TRY(s.upload(&d_err, err, (size_t)K));
-    TRY(s.upload(&d_len, (const int*)nullptr, (size_t)n_pts)); TRY(s.upload(&d_ks, (const double*)nullptr, (size_t)n_pts));
-    TRY(s.upload(&d_kc, (const double*)nullptr, (size_t)n_pts));
+    TRY(s.alloc(&d_len, (size_t)n_pts)); TRY(s.alloc(&d_ks, (size_t)n_pts));
+    TRY(s.alloc(&d_kc, (size_t)n_pts));
     if (n_pts) {
         hipLaunchKernelGGL(k_trk_keys, dim3((unsigned)((n_pts + TRK_THREADS - 1) / TRK_THREADS)), dim3(TRK_THREADS), 0, s.stream, (int)n_pts, d_ofs,
                            d_scale, d_err, d_len, d_ks, d_kc, (unsigned long long*)nullptr);
@@ -108,7 +87,7 @@ int satba_track_connectivity(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs
     std::vector<int> ofs32;
     TRY(trk_check_lists(n_cam, n_pts, pt_ofs, cam_ind, ofs32, nullptr));
     const int64_t K = pt_ofs[n_pts];
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     int *d_ofs, *d_cam, *d_alive = nullptr, *d_tri, *d_A;
     TRY(s.upload(&d_ofs, ofs32.data(), ofs32.size())); TRY(s.upload(&d_cam, cam_ind, (size_t)K));
@@ -119,8 +98,8 @@ int satba_track_connectivity(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs
         HIP_TRY(hipStreamSynchronize(s.stream));  // a32 leaves scope
     }
     const int M = n_cam;
-    TRY(s.upload(&d_tri, (const int*)nullptr, (size_t)std::max(M * (M - 1) / 2, 1))); TRY(s.upload(&d_A, (const int*)nullptr, (size_t)M * M));
-    TRY(trk_connect(s, (int)n_pts, M, d_ofs, d_cam, d_alive, 1, d_tri, trk_lds_limit(device)));
+    TRY(s.alloc(&d_tri, (size_t)std::max(M * (M - 1) / 2, 1))); TRY(s.alloc(&d_A, (size_t)M * M));
+    TRY(trk_connect(s, (int)n_pts, M, d_ofs, d_cam, d_alive, 1, d_tri, dev_lds_limit(device)));
     hipLaunchKernelGGL(k_trk_connect_finish, dim3((unsigned)(((long long)M * M + TRK_THREADS - 1) / TRK_THREADS)), dim3(TRK_THREADS), 0, s.stream, M,
                        d_tri, (int)min_matches, d_A);
     HIP_TRY(hipGetLastError());
@@ -146,9 +125,9 @@ int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, con
     std::vector<int> cam_ofs((size_t)M + 1, 0);
     for (int c = 0; c < M; ++c) cam_ofs[(size_t)c + 1] = cam_ofs[(size_t)c] + cam_cnt[(size_t)c];
 
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
-    const int lds_optin = trk_lds_limit(device);
+    const int lds_optin = dev_lds_limit(device);
     int *d_ofs, *d_cam, *d_len, *d_idx_a, *d_idx_b, *d_rank, *d_tree, *d_cam_ofs, *d_cm_trk, *d_cam_sorted, *d_obs_trk, *d_tri, *d_reached, *d_layer, *d_status;
     double *d_scale, *d_err = nullptr, *d_ks, *d_kc, *d_w, *d_wout = nullptr;
     unsigned long long *d_img, *d_key_a, *d_key_b, *d_slot;
@@ -156,18 +135,18 @@ int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, con
     TRY(s.upload(&d_scale, scale, (size_t)n_obs));
     if (err) TRY(s.upload(&d_err, err, (size_t)n_obs));
     TRY(s.upload(&d_cam_ofs, cam_ofs.data(), cam_ofs.size()));
-    TRY(s.upload(&d_len, (const int*)nullptr, (size_t)N)); TRY(s.upload(&d_ks, (const double*)nullptr, (size_t)N));
-    TRY(s.upload(&d_kc, (const double*)nullptr, (size_t)N)); TRY(s.upload(&d_img, (const unsigned long long*)nullptr, 3 * (size_t)N));
-    TRY(s.upload(&d_key_a, (const unsigned long long*)nullptr, (size_t)N)); TRY(s.upload(&d_key_b, (const unsigned long long*)nullptr, (size_t)N));
-    TRY(s.upload(&d_idx_a, (const int*)nullptr, (size_t)N)); TRY(s.upload(&d_idx_b, (const int*)nullptr, (size_t)N));
-    TRY(s.upload(&d_rank, (const int*)nullptr, (size_t)N)); TRY(s.upload(&d_tree, (const int*)nullptr, (size_t)N));
-    TRY(s.upload(&d_cm_trk, (const int*)nullptr, (size_t)n_obs)); TRY(s.upload(&d_cam_sorted, (const int*)nullptr, (size_t)n_obs));
-    TRY(s.upload(&d_obs_trk, (const int*)nullptr, (size_t)n_obs));
-    TRY(s.upload(&d_tri, (const int*)nullptr, (size_t)std::max(M * (M - 1) / 2, 1)));
-    TRY(s.upload(&d_reached, (const int*)nullptr, (size_t)M)); TRY(s.upload(&d_layer, (const int*)nullptr, (size_t)M));
-    TRY(s.upload(&d_slot, (const unsigned long long*)nullptr, (size_t)M)); TRY(s.upload(&d_w, (const double*)nullptr, (size_t)M));
-    TRY(s.upload(&d_status, (const int*)nullptr, (size_t)TRK_ST_LEN));
-    if (weights && K) TRY(s.upload(&d_wout, (const double*)nullptr, (size_t)K * M));
+    TRY(s.alloc(&d_len, (size_t)N)); TRY(s.alloc(&d_ks, (size_t)N));
+    TRY(s.alloc(&d_kc, (size_t)N)); TRY(s.alloc(&d_img, 3 * (size_t)N));
+    TRY(s.alloc(&d_key_a, (size_t)N)); TRY(s.alloc(&d_key_b, (size_t)N));
+    TRY(s.alloc(&d_idx_a, (size_t)N)); TRY(s.alloc(&d_idx_b, (size_t)N));
+    TRY(s.alloc(&d_rank, (size_t)N)); TRY(s.alloc(&d_tree, (size_t)N));
+    TRY(s.alloc(&d_cm_trk, (size_t)n_obs)); TRY(s.alloc(&d_cam_sorted, (size_t)n_obs));
+    TRY(s.alloc(&d_obs_trk, (size_t)n_obs));
+    TRY(s.alloc(&d_tri, (size_t)std::max(M * (M - 1) / 2, 1)));
+    TRY(s.alloc(&d_reached, (size_t)M)); TRY(s.alloc(&d_layer, (size_t)M));
+    TRY(s.alloc(&d_slot, (size_t)M)); TRY(s.alloc(&d_w, (size_t)M));
+    TRY(s.alloc(&d_status, (size_t)TRK_ST_LEN));
+    if (weights && K) TRY(s.alloc(&d_wout, (size_t)K * M));
     HIP_TRY(hipMemsetAsync(d_tree, 0xff, sizeof(int) * (size_t)std::max(N, 1), s.stream));  // -1: not selected
     HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int) * TRK_ST_LEN, s.stream));
     if (d_wout) HIP_TRY(hipMemsetAsync(d_wout, 0, sizeof(double) * (size_t)K * M, s.stream));
@@ -178,7 +157,7 @@ int satba_select_tracks(int32_t n_cam, int64_t n_pts, const int64_t* pt_ofs, con
     if (n_obs) HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_b, d_cam, d_cam_sorted, d_obs_trk, d_cm_trk, (size_t)n_obs, 0, 32, s.stream));
     char* d_tmp;
     const size_t tmp_bytes = std::max(tmp_a, tmp_b) + 16;
-    TRY(s.upload(&d_tmp, (const char*)nullptr, tmp_bytes));
+    TRY(s.alloc(&d_tmp, tmp_bytes));
 
     const dim3 gN((unsigned)((N + TRK_THREADS - 1) / TRK_THREADS)), blk(TRK_THREADS);
     HIP_TRY(hipEventRecord(s.e0, s.stream));

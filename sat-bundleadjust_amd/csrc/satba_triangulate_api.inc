@@ -2,30 +2,6 @@
 // Stand-alone entry points (no problem handle): the triangulation runs before a BundleAdjustmentParameters object exists.
 extern "C++" {
 namespace {
-struct TriScratch {
-    std::vector<void*> ptrs;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~TriScratch() {
-        for (void* q : ptrs) (void)hipFree(q);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    template <class T>
-    int upload(T** d, const T* h, size_t n) {
-        HIP_TRY(hipMalloc((void**)d, (n ? n : 1) * sizeof(T)));
-        ptrs.push_back(*d);
-        if (h && n) HIP_TRY(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, stream));
-        return 0;
-    }
-    int begin(int device) {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamCreate(&stream));
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        return 0;
-    }
-};
 int tri_cam_len(int model) { return model == SATBA_RPC ? SATBA_RPC_TABLE_LEN : 12; }
 }  // namespace
 }  // extern "C++"
@@ -34,15 +10,15 @@ int satba_triangulate_pairwise(int32_t cam_model, const double* cam_i, const dou
                                double* pts3d, float* err, int32_t device, float* kernel_ms) {
     if (!cam_i || !cam_j || n < 0 || (n && (!pts_i || !pts_j || !pts3d))) return fail(SATBA_E_ARG, "null argument");
     if (cam_model != SATBA_AFFINE && cam_model != SATBA_PERSPECTIVE && cam_model != SATBA_RPC) return fail(SATBA_E_ARG, "unknown camera model");
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     const int len = tri_cam_len(cam_model);
     double *d_ci, *d_cj, *d_pi, *d_pj, *d_out;
     float* d_err = nullptr;
     TRY(s.upload(&d_ci, cam_i, (size_t)len)); TRY(s.upload(&d_cj, cam_j, (size_t)len));
     TRY(s.upload(&d_pi, pts_i, (size_t)2 * n)); TRY(s.upload(&d_pj, pts_j, (size_t)2 * n));
-    TRY(s.upload(&d_out, (const double*)nullptr, (size_t)3 * n));
-    if (err) TRY(s.upload(&d_err, (const float*)nullptr, (size_t)n));
+    TRY(s.alloc(&d_out, (size_t)3 * n));
+    if (err) TRY(s.alloc(&d_err, (size_t)n));
     HIP_TRY(hipEventRecord(s.e0, s.stream));
     if (n) {
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -62,7 +38,7 @@ extern "C++" {
 namespace {
 // the four passes over prepared arguments (a: pt_ofs, cam_ind, obs and, for a handle's layout, slice_base / removed / perm set by the
 // caller; the pair tables, outputs and work lists are set up here); results to the host
-int tri_run(TriScratch& s, TriArgs a, int32_t cam_model, int32_t n_cam, int64_t n_pts, bool ordered, const double* cameras, int32_t n_pairs,
+int tri_run(DevRun& s, TriArgs a, int32_t cam_model, int32_t n_cam, int64_t n_pts, bool ordered, const double* cameras, int32_t n_pairs,
             const int32_t* pairs, const std::vector<int>& first, const std::vector<int>& next, float* pts3d, int32_t* n_tri, int32_t device,
             int32_t reps, float* kernel_ms) {
     a.M = n_cam; a.N = (int)n_pts; a.n_pairs = n_pairs; a.cam_len = tri_cam_len(cam_model); a.ordered = ordered;
@@ -71,30 +47,23 @@ int tri_run(TriScratch& s, TriArgs a, int32_t cam_model, int32_t n_cam, int64_t 
     float* d_out;
     TRY(s.upload(&d_cams, cameras, (size_t)n_cam * a.cam_len)); TRY(s.upload(&d_first, first.data(), first.size()));
     TRY(s.upload(&d_next, next.data(), next.size())); TRY(s.upload(&d_pairs, pairs, (size_t)2 * n_pairs));
-    TRY(s.upload(&d_out, (const float*)nullptr, (size_t)3 * n_pts));
-    TRY(s.upload(&d_ntri, (const int*)nullptr, (size_t)n_pts + 1)); TRY(s.upload(&d_tofs, (const int*)nullptr, (size_t)n_pts + 1));
-    if (a.perm && n_tri) TRY(s.upload(&d_ntri_out, (const int*)nullptr, (size_t)n_pts));
+    TRY(s.alloc(&d_out, (size_t)3 * n_pts));
+    TRY(s.alloc(&d_ntri, (size_t)n_pts + 1)); TRY(s.alloc(&d_tofs, (size_t)n_pts + 1));
+    if (a.perm && n_tri) TRY(s.alloc(&d_ntri_out, (size_t)n_pts));
     HIP_TRY(hipMemsetAsync(d_ntri, 0, sizeof(int) * ((size_t)n_pts + 1), s.stream));
     a.cams = d_cams; a.pair_first = d_first; a.pair_next = d_next; a.pairs = d_pairs;
     a.out = d_out; a.n_tri = d_ntri; a.tri_ofs = d_tofs; a.n_tri_out = d_ntri_out;
     const size_t tab_bytes = sizeof(double) * (size_t)n_cam * TRI_RPC_STRIDE;
     // the RPC tables go to dynamic LDS when the device's opt-in limit allows (160 KB per workgroup on gfx950; the limit is asked,
     // not assumed: the Makefile's ARCH can be overridden), with 20 KB left for the kernel's own arrays
-    int lds_optin = 0;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-            lds_optin = (int)std::max(prop.sharedMemPerBlockOptin, prop.sharedMemPerBlock);
-            if (strstr(prop.gcnArchName, "gfx950")) lds_optin = std::max(lds_optin, 160 * 1024);  // CDNA4: 160 KB per workgroup
-        }
-    }
+    const int lds_optin = dev_lds_limit(device);
     const bool tab_lds = cam_model == SATBA_RPC && (long long)tab_bytes + 20 * 1024 <= (long long)lds_optin;
     if (tab_lds && tab_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tri_points<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes));
-    void* d_cub = nullptr;
+    char* d_cub = nullptr;
     size_t cub_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, d_ntri, d_tofs, (int)n_pts + 1, s.stream));
-    TRY(s.upload((char**)&d_cub, (const char*)nullptr, cub_bytes + 16));
+    TRY(s.alloc(&d_cub, cub_bytes + 16));
     const dim3 g256((unsigned)((n_pts + 255) / 256)), gl((unsigned)((n_pts + TRI_THREADS - 1) / TRI_THREADS));
     auto count_pass = [&]() -> int {
         hipLaunchKernelGGL(k_tri_count, g256, dim3(256), 0, s.stream, a);
@@ -113,7 +82,7 @@ int tri_run(TriScratch& s, TriArgs a, int32_t cam_model, int32_t n_cam, int64_t 
     }
     int2* d_entries;
     float* d_res;
-    TRY(s.upload(&d_entries, (const int2*)nullptr, (size_t)E)); TRY(s.upload(&d_res, (const float*)nullptr, (size_t)3 * E));
+    TRY(s.alloc(&d_entries, (size_t)E)); TRY(s.alloc(&d_res, (size_t)3 * E));
     a.entries = d_entries; a.res = d_res;
     reps = std::max(reps, 1);
     HIP_TRY(hipEventRecord(s.e0, s.stream));
@@ -166,14 +135,9 @@ int satba_init_pts3d(int32_t cam_model, int32_t n_cam, int64_t n_pts, const int6
     if (n_cam <= 0 || n_pts < 0 || n_pairs < 0 || !pt_ofs || !cameras || (n_pts && !pts3d) || (n_pairs && !pairs))
         return fail(SATBA_E_ARG, "null or negative argument");
     if (cam_model != SATBA_AFFINE && cam_model != SATBA_PERSPECTIVE && cam_model != SATBA_RPC) return fail(SATBA_E_ARG, "unknown camera model");
+    std::vector<int> ofs32;
+    TRY(dev_check_offsets(n_pts, pt_ofs, cam_ind && obs, ofs32));
     const int64_t K = pt_ofs[n_pts];
-    if (pt_ofs[0] != 0 || K < 0 || K >= (int64_t)1 << 31 || n_pts >= (int64_t)1 << 31) return fail(SATBA_E_ARG, "offsets out of range");
-    if (K && (!cam_ind || !obs)) return fail(SATBA_E_ARG, "null observations");
-    std::vector<int> ofs32((size_t)n_pts + 1);
-    for (int64_t i = 0; i <= n_pts; ++i) {
-        if (i && pt_ofs[i] < pt_ofs[i - 1]) return fail(SATBA_E_ARG, "pt_ofs must not decrease");
-        ofs32[(size_t)i] = (int)pt_ofs[i];
-    }
     for (int64_t o = 0; o < K; ++o)
         if (cam_ind[o] < 0 || cam_ind[o] >= n_cam) return fail(SATBA_E_ARG, "camera index %d out of range", cam_ind[o]);
     // the common case: pairs listed in ascending lexicographic order with c_i < c_j, every track's cameras ascending
@@ -183,7 +147,7 @@ int satba_init_pts3d(int32_t cam_model, int32_t n_cam, int64_t n_pts, const int6
     for (int64_t i = 0; i < n_pts && ordered; ++i)
         for (int64_t o = pt_ofs[i] + 1; o < pt_ofs[i + 1]; ++o)
             if (cam_ind[o] <= cam_ind[o - 1]) { ordered = false; break; }
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(device));
     TriArgs a{};
     int *d_ofs, *d_cam;
@@ -201,7 +165,7 @@ int satba_init_pts3d_resident(satba_problem* p, const uint8_t* remove, const dou
     bool ordered = getenv("SATBA_TRI_GENERAL") == nullptr;
     std::vector<int> first, next;
     TRY(tri_pair_tables(p->M, n_pairs, pairs, first, next, ordered));
-    TriScratch s;
+    DevRun s;
     TRY(s.begin(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));  // (the layout is static, but a caller may still have work queued on the handle)
     const Layout& L = p->L;
@@ -211,7 +175,7 @@ int satba_init_pts3d_resident(satba_problem* p, const uint8_t* remove, const dou
     if (remove && p->K) {
         unsigned char *d_rm, *d_rm_ell;
         TRY(s.upload(&d_rm, (const unsigned char*)remove, (size_t)p->K));
-        TRY(s.upload(&d_rm_ell, (const unsigned char*)nullptr, (size_t)std::max(L.P, 1) + 64));
+        TRY(s.alloc(&d_rm_ell, (size_t)std::max(L.P, 1) + 64));
         HIP_TRY(hipMemsetAsync(d_rm_ell, 0, (size_t)std::max(L.P, 1) + 64, s.stream));
         hipLaunchKernelGGL(k_tri_mask_ell, dim3((unsigned)((p->K + 255) / 256)), dim3(256), 0, s.stream, p->K, L.obs_pos, d_rm, d_rm_ell);
         HIP_TRY(hipGetLastError());
