@@ -545,6 +545,44 @@ int satba_rpc_fundamental(int32_t n_cam, const double *tables, int32_t n_pairs, 
                           double *F5, double *sv, double *matches, uint8_t *degenerate, int32_t device);
 double satba_rpc_fundamental_kernel_ms(void);
 
+/* ---- fundamental-matrix RANSAC of the pairwise matches (the filter of ref:bundle_adjust/s2p/sift.py:181-184 and of
+ * ref:feature_tracks/ft_opencv.py:188-216).  Stand-alone: no problem handle, float64, all pairs of a call in
+ * three launches.  The reference's RANSACs are random and in neither tree, so the rule is fixed here; it is deterministic, and a
+ * pair's result depends on its rows, its index p in the call, n_trials, max_err and seed only.
+ * Input per pair p: its M_p = pair_ofs[p + 1] - pair_ofs[p] matches as rows (x1, y1, x2, y2), in the caller's order.
+ * 1. Small pairs.  M_p < 7: every match is kept, no model, best = (-1, M_p, 0).
+ * 2. Normalisation.  Per pair and side Hartley's: translate to the centroid, scale so that the mean distance is sqrt(2); once, in
+ *    float64, sums in the caller's order.  If a side's mean distance is 0 every match is kept and there is no model.
+ * 3. Sampling, counter based.  Draw k of trial t of pair p is z = splitmix64(seed + 0x9E3779B97F4A7C15 * (1 + ((p * n_trials + t)
+ *    * 64 + k))) in 64-bit wrap-around arithmetic (splitmix64: the finaliser z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *    z *= 0x94D049BB133111EB, z ^= z >> 31); the index is ((z >> 32) * M_p) >> 32.  Draws k = 0, 1, ... are taken until seven
+ *    distinct indices are found, a repeat is skipped; after 64 draws without seven distinct indices the trial gives no model.  A
+ *    sample in which two matches have a bit-identical (x1, y1) or a bit-identical (x2, y2) gives no model.
+ * 4. Seven-point models.  The 7 x 9 matrix has the rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] of the normalised points;
+ *    F1, F2 span its null space (Gauss-Jordan elimination with full pivoting, each vector of unit length); the real roots x of
+ *    det(x F1 + (1 - x) F2) = 0 (closed form; three roots when the discriminant of the depressed cubic is negative, else one; a
+ *    leading coefficient below 1e-12 of the largest drops the degree; then four Newton steps per root) give one to three models per
+ *    trial, each denormalised (T2^T F T1) and scaled to unit Frobenius norm; a matrix that is not finite is no model.
+ * 5. Error of a match under F: the larger of the two squared point-to-epipolar-line distances in pixel coordinates, as
+ *    ref:ft_opencv.py:143-185 computes it, every operation rounded on its own.  Inlier iff err < max_err^2.
+ * 6. Winner: the model with the most inliers; ties go to the lowest trial; ties between roots of one trial to the smaller sum of err
+ *    over the model's inliers (then to the root written first).  The mask is the winner's inlier set; no refit.  If no trial gave a
+ *    model every match is kept.
+ * 7. The reference's values: n_trials = 1000 (sift.py:182), max_err = FT_ransac (0.3); seed is the caller's.
+ * Outputs: inlier (n = pair_ofs[n_pairs]; 1 kept, 0 dropped); F (n_pairs x 9, may be NULL; zeros where there is no model); best
+ * (n_pairs x 3, may be NULL) = winning trial (-1: no model), matches kept, models of the pair over all trials; kernel_ms (may be NULL):
+ * HIP events around the three launches.
+ * SATBA_E_ARG: a negative n_pairs, a pair_ofs that does not start at 0 or decreases, a non-finite coordinate, max_err <= 0 or not
+ * finite, n_trials outside 1..65536, NULL pair_ofs (n_pairs > 0) or NULL xy / inlier (n > 0), n_pairs * n_trials above 2^26 or
+ * n >= 2^31.  n_pairs == 0 and n == 0 return 0 without a device call. */
+int satba_ransac_fundamental(int32_t n_pairs, const int64_t *pair_ofs, const double *xy, double max_err, int32_t n_trials, uint64_t seed,
+                             uint8_t *inlier, double *F, int32_t *best, int32_t device, float *kernel_ms);
+/* test entry: the models (step 4) of given samples, no sampling.  xy: the m rows of one pair (normalised as in step 2); idx
+ * (n_samples x 7) indexes them -> n_models (n_samples), F (n_samples x 3 x 9, zeros behind the models).  A sample with repeated
+ * points (step 3) or a pair without a normalisation gives 0 models.  SATBA_E_ARG: NULL, an index outside 0..m-1, a non-finite
+ * coordinate. */
+int satba_ransac_models(int64_t m, const double *xy, int32_t n_samples, const int32_t *idx, int32_t *n_models, double *F, int32_t device);
+
 /* ---- inspection entry points (parity tests; not used by the solver loop) */
 /* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64): n must equal satba_layout_len */
 enum { SATBA_LAY_PERM = 0, SATBA_LAY_RANK, SATBA_LAY_PT_CNT, SATBA_LAY_SLICE_BASE, SATBA_LAY_E_CAM, SATBA_LAY_OBS_POS, SATBA_LAY_CAM_OFS,

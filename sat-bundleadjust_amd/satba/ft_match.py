@@ -16,9 +16,15 @@ first keypoint with the same (col, row) -- SIFT emits one keypoint per orientati
 reproduces that with one index map per image (keypoints that share a location share their UTM coordinates, so they are inside a
 box together); `canonical=False` returns the matched rows themselves.
 
-Not reproduced: the RANSAC of the reference (`ransac.find_fundamental_matrix` / `cv2.findFundamentalMat`) is random and in neither
-tree; `geometric_filter`, a callable (pix_i, pix_j, matches_ij) -> boolean mask, takes its place when a caller wants one.  The
-pairwise .npy cache files are not read or written, and only "epipolar_based" and "bruteforce" are matched here.
+Geometric filter.  ref:bundle_adjust/s2p/sift.py:181-184 and ref:feature_tracks/ft_opencv.py:188-216 filter every pair's matches by a
+fundamental-matrix RANSAC (`ransac.find_fundamental_matrix` / `cv2.findFundamentalMat`) that is random and in neither tree.
+`geometric_filter="ransac"` runs the deterministic rule of include/satba.h (satba_ransac_fundamental: counter-based samples,
+seven-point models, the reference's error, most inliers wins; csrc/satba_ransac.h) on the device, all pairs of a call
+in one device call, with max_err = FT_ransac (0.3), 1000 trials and `ransac_seed`.  A callable (pix_i, pix_j, matches_ij) ->
+boolean mask is taken as before; None (the default) filters nothing.  `ransac_fundamental`, `geometric_filtering` and
+`inliers_mask_from_fundamental_matrix` are the pieces on their own, the last two under the reference's names.
+
+Not reproduced: the pairwise .npy cache files are not read or written, and only "epipolar_based" and "bruteforce" are matched here.
 """
 import ctypes as ct
 
@@ -255,14 +261,98 @@ def _method(tracks_config):
     return method
 
 
-def _after_match(m_ij, feats_i, feats_j, utm_i, utm_j, maps, canonical, geometric_filter):
-    """renaming, the caller's geometric filter, the UTM filter: one pair on the host (a pair has few matches)"""
-    n = [m_ij.shape[0]]
+def ransac_fundamental(pair_ofs, xy, max_err=0.3, n_trials=1000, seed=0, device=None, return_info=False):
+    """
+    satba_ransac_fundamental (include/satba.h): the matches of all pairs, rows (x1, y1, x2, y2) in float64, pair p being rows
+    pair_ofs[p] : pair_ofs[p + 1].  Returns the boolean mask of the matches kept; with return_info also a dict: F (n_pairs, 3, 3;
+    zeros where a pair has no model), best (n_pairs, 3) = winning trial (-1: none), matches kept, models tried, and kernel_ms.
+    """
+    pair_ofs = np.ascontiguousarray(np.asarray(pair_ofs, dtype=np.int64).reshape(-1))
+    xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 4))
+    if pair_ofs.size < 1 or pair_ofs[-1] != xy.shape[0]:
+        raise ValueError("pair_ofs must hold n_pairs + 1 offsets that end at the number of matches ({}), got {}".format(xy.shape[0], pair_ofs[-1:]))
+    n_pairs = pair_ofs.size - 1
+    inlier = np.zeros(xy.shape[0], dtype=np.uint8)
+    F, best = np.zeros((n_pairs, 9), dtype=np.float64), np.zeros((n_pairs, 3), dtype=np.int32)
+    lib = E.load_library()
+    ms = ct.c_float(0.0)
+    E._check(lib, lib.satba_ransac_fundamental(n_pairs, pair_ofs.ctypes.data_as(_lp), E._ptr(xy), float(max_err), int(n_trials), int(seed) & (2 ** 64 - 1),
+                                               inlier.ctypes.data_as(ct.POINTER(ct.c_uint8)), E._ptr(F), E._ptr(best, E._ip), _device(device), ct.byref(ms)))
+    mask = inlier.astype(bool)
+    if return_info:
+        return mask, {"F": F.reshape(n_pairs, 3, 3), "best": best, "kernel_ms": ms.value}
+    return mask
+
+
+def inliers_mask_from_fundamental_matrix(F, m1, m2, ransac_thr):
+    """ref:feature_tracks/ft_opencv.py:143-185: the matches (m1, m2: N x 2) whose larger squared distance to the epipolar lines of F
+    is below ransac_thr ** 2 (None: 3.0, cv2's default); None when no match is."""
+    F_ = np.asarray(F, dtype=np.float64).reshape(-1)
+    m1, m2 = np.asarray(m1, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+    assert m1.shape[1] == 2 and m2.shape[1] == 2 and m1.shape == m2.shape
+    ransac_thr = 3.0 if ransac_thr is None else ransac_thr
+    with np.errstate(all="ignore"):
+        a = F_[0] * m1[:, 0] + F_[1] * m1[:, 1] + F_[2]
+        b = F_[3] * m1[:, 0] + F_[4] * m1[:, 1] + F_[5]
+        c = F_[6] * m1[:, 0] + F_[7] * m1[:, 1] + F_[8]
+        s2 = 1.0 / (a * a + b * b)
+        d2 = m2[:, 0] * a + m2[:, 1] * b + c
+        a = F_[0] * m2[:, 0] + F_[3] * m2[:, 1] + F_[6]
+        b = F_[1] * m2[:, 0] + F_[4] * m2[:, 1] + F_[7]
+        c = F_[2] * m2[:, 0] + F_[5] * m2[:, 1] + F_[8]
+        s1 = 1.0 / (a * a + b * b)
+        d1 = m1[:, 0] * a + m1[:, 1] * b + c
+        inliers_mask = np.maximum(d1 * d1 * s1, d2 * d2 * s2) < ransac_thr ** 2
+    return inliers_mask if inliers_mask.any() else None
+
+
+def _match_coords(features_i, features_j, matches_ij):
+    return np.concatenate([np.asarray(features_i)[matches_ij[:, 0], :2], np.asarray(features_j)[matches_ij[:, 1], :2]], axis=1).astype(np.float64)
+
+
+def geometric_filtering(features_i, features_j, matches_ij, ransac_thr=0.3, return_mask=False, seed=0, device=None):
+    """ref:feature_tracks/ft_opencv.py:188-216 with the device RANSAC in place of cv2's: the rows of matches_ij (M x 2) that the
+    winning model keeps, None when there is none; ransac_thr=None means 3.0, cv2's default.  With return_mask also the M x 1 uint8
+    mask (None with no match)."""
+    matches_ij = np.asarray(matches_ij).reshape(-1, 2)
+    mask = None
+    if matches_ij.shape[0]:
+        mask = ransac_fundamental([0, matches_ij.shape[0]], _match_coords(features_i, features_j, matches_ij),
+                                  max_err=3.0 if ransac_thr is None else ransac_thr, seed=seed, device=device)
+    matches_ij = matches_ij[mask] if mask is not None and mask.any() else None
+    if return_mask:
+        return matches_ij, (mask.astype(np.uint8).reshape(-1, 1) if mask is not None else None)
+    return matches_ij
+
+
+def _check_filter(geometric_filter):
+    if not (geometric_filter is None or geometric_filter == "ransac" or callable(geometric_filter)):
+        raise ValueError('geometric_filter must be None, "ransac" or a callable, got {!r}'.format(geometric_filter))
+
+
+def _rename(m_ij, maps, canonical):
     if m_ij.shape[0] and canonical:
         m_ij = np.stack([maps[0][m_ij[:, 0]], maps[1][m_ij[:, 1]]], axis=1)
+    return m_ij
+
+
+def _ransac_masks(jobs, tracks_config, seed, device):
+    """the masks of all pairs (jobs: (m_ij, feats_i, feats_j) per pair, renamed) from one device call, and its kernel time"""
+    ofs = np.cumsum([0] + [m_ij.shape[0] for m_ij, _, _ in jobs]).astype(np.int64)
+    if ofs[-1] == 0:
+        return [np.zeros(0, dtype=bool) for _ in jobs], 0.0
+    xy = np.concatenate([_match_coords(fi, fj, m_ij) for m_ij, fi, fj in jobs if m_ij.shape[0]], axis=0)
+    mask, info = ransac_fundamental(ofs, xy, max_err=tracks_config.get("FT_ransac", 0.3), seed=seed, device=device, return_info=True)
+    return [mask[ofs[k]:ofs[k + 1]] for k in range(len(jobs))], info["kernel_ms"]
+
+
+def _after_match(m_ij, feats_i, feats_j, utm_i, utm_j, geometric_filter, mask=None):
+    """the geometric filter (a callable, or the mask the device RANSAC gave) and the UTM filter of one renamed pair on the host"""
+    n = [m_ij.shape[0]]
     if m_ij.shape[0] and geometric_filter is not None:
-        mask = np.asarray(geometric_filter(np.asarray(feats_i[:, :2]), np.asarray(feats_j[:, :2]), m_ij), dtype=bool).reshape(-1)
-        m_ij = m_ij[mask]
+        if mask is None:
+            mask = geometric_filter(np.asarray(feats_i[:, :2]), np.asarray(feats_j[:, :2]), m_ij)
+        m_ij = m_ij[np.asarray(mask, dtype=bool).reshape(-1)]
         n.append(m_ij.shape[0])
     if m_ij.shape[0]:
         m_ij = filter_matches_inconsistent_utm_coords(m_ij, utm_i, utm_j)
@@ -278,10 +368,12 @@ def _polygon_box(utm_polygon):
 
 
 def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygon, tracks_config, F=None, canonical=True, geometric_filter=None,
-                                device=None):
+                                device=None, ransac_seed=0):
     """ref:ft_match.py:93-187 for one pair.  utm_polygon: a ring (n, 2), a geojson polygon, or an object with .exterior.coords.
-    Returns (matches_ij (M, 2) or None, n): n = [matched, after the UTM filter], or [0, 0, 0] when a side has no keypoint inside."""
+    Returns (matches_ij (M, 2) or None, n): n = [matched, after the geometric filter when there is one, after the UTM filter], or
+    [0, 0, 0] when a side has no keypoint inside."""
     method = _method(tracks_config)
+    _check_filter(geometric_filter)
     box = _polygon_box(utm_polygon)
     fi, fj, ui, uj = _load(features_i, np.float32, 132), _load(features_j, np.float32, 132), _load(utm_i, np.float64, 2), _load(utm_j, np.float64, 2)
     if box is None:
@@ -294,18 +386,23 @@ def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygo
     if info["n_empty_pairs"]:
         return None, [0, 0, 0]
     maps = (canonical_index_map(fi), canonical_index_map(fj)) if canonical else None
-    m_ij, n = _after_match(np.stack([kp_i, kp_j], axis=1).astype(np.int64), fi, fj, ui, uj, maps, canonical, geometric_filter)
+    m_ij = _rename(np.stack([kp_i, kp_j], axis=1).astype(np.int64), maps, canonical)
+    mask = _ransac_masks([(m_ij, fi, fj)], tracks_config, ransac_seed, device)[0][0] if geometric_filter == "ransac" else None
+    m_ij, n = _after_match(m_ij, fi, fj, ui, uj, geometric_filter, mask)
     return (m_ij if m_ij.shape[0] else None), n
 
 
 def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_config, F=None, canonical=True, geometric_filter=None,
-                       device=None, return_info=False):
+                       device=None, return_info=False, ransac_seed=0):
     """
     ref:ft_match.py:250-339.  features / utm_coords: per image an array or a .npy path; footprints: per image a dict with a
     "geojson" polygon in UTM coordinates (convex).  F: per pair a 3 x 3 fundamental matrix ("epipolar_based").  Returns the M x 4
     int64 array (kp_i, kp_j, im_i, im_j), pairs in the given order; a pair whose footprints share no area gives no rows.
+    geometric_filter: None, a callable per pair, or "ransac": the device RANSAC over all pairs in one call (module docstring), whose
+    kernel time return_info reports as "ransac_kernel_ms".
     """
     method = _method(tracks_config)
+    _check_filter(geometric_filter)
     pairs = [(int(p[0]), int(p[1])) for p in pairs_to_match]
     if method == "epipolar_based" and (F is None or len(F) != len(pairs)):
         raise ValueError("epipolar_based matching needs one fundamental matrix per pair")
@@ -323,11 +420,18 @@ def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_
         ofs, kp_i, kp_j, info = match_pairs([pairs[k] for k in live], feats, utms, [boxes[k] for k in live], F=Fs,
                                             thr=tracks_config.get("FT_rel_thr", 0.6), device=device, return_info=True)
         maps = {c: canonical_index_map(feats[c]) for c in used} if canonical else None
-        rows = []
+        jobs = []
         for m, k in enumerate(live):
             i, j = pairs[k]
             m_ij = np.stack([kp_i[ofs[m]:ofs[m + 1]], kp_j[ofs[m]:ofs[m + 1]]], axis=1).astype(np.int64)
-            m_ij, _ = _after_match(m_ij, feats[i], feats[j], utms[i], utms[j], (maps[i], maps[j]) if canonical else None, canonical, geometric_filter)
+            jobs.append((_rename(m_ij, (maps[i], maps[j]) if canonical else None, canonical), feats[i], feats[j]))
+        masks = [None] * len(jobs)
+        if geometric_filter == "ransac":
+            masks, info["ransac_kernel_ms"] = _ransac_masks(jobs, tracks_config, ransac_seed, device)
+        rows = []
+        for (m_ij, _, _), mask, k in zip(jobs, masks, live):
+            i, j = pairs[k]
+            m_ij, _ = _after_match(m_ij, feats[i], feats[j], utms[i], utms[j], geometric_filter, mask)
             if m_ij.shape[0]:
                 rows.append(np.concatenate([m_ij, np.tile(np.array([[i, j]], dtype=np.int64), (m_ij.shape[0], 1))], axis=1))
         if rows:
