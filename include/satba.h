@@ -583,6 +583,40 @@ int satba_ransac_fundamental(int32_t n_pairs, const int64_t *pair_ofs, const dou
  * coordinate. */
 int satba_ransac_models(int64_t m, const double *xy, int32_t n_samples, const int32_t *idx, int32_t *n_models, double *F, int32_t device);
 
+/* ---- the geographic side of the pairwise matching.  Stand-alone: no problem handle, float64.
+ * satba_utm_filter is ref:feature_tracks/ft_match.py:220-247 (`filter_matches_inconsistent_utm_coords`) for the matches of all
+ * pairs of a call: pair p owns the rows pair_ofs[p] : pair_ofs[p + 1] of utm (host, n x 4: east_i, north_i, east_j, north_j of the
+ * match's two keypoints).  Per pair, over its matches with alive != 0 (alive NULL: all of them; a geometric filter's mask can be
+ * handed in as it is):
+ *   d = sqrt(dx * dx + dy * dy), every operation rounded on its own (what np.linalg.norm(..., axis=1) does on two columns);
+ *   v = sort(d); (elbow, success) = get_elbow_value(v, 20) (ref:bundle_adjust/ba_outliers.py:14-58: the value farthest from the
+ *   chord, first maximum; success iff elbow >= the 80th percentile, numpy's "linear" method); thr = success ? elbow + margin :
+ *   v[last]; keep = d <= thr.  Index-exact against numpy, also where only rounding decides.
+ * A match with alive == 0 gets keep = 0 and takes no part in the curve; a pair without an alive match gets thr = NaN, n_kept = 0.
+ * Outputs (host): keep (n bytes, the caller's order), thr (n_pairs, may be NULL), n_kept (n_pairs, may be NULL); kernel_ms (may be
+ * NULL): HIP events from the first kernel to the last.  margin: the reference's is 5.0 m.
+ * SATBA_E_ARG: a negative n_pairs, a pair_ofs that does not start at 0 or decreases, n >= 2^31, a non-finite coordinate of an
+ * alive match, a negative or non-finite margin, NULL pair_ofs (n_pairs > 0) or NULL utm / keep (n > 0).  n_pairs == 0 and n == 0
+ * return 0 without a device call. */
+int satba_utm_filter(int32_t n_pairs, const int64_t *pair_ofs, const double *utm /* n x 4: east_i, north_i, east_j, north_j */,
+                     const uint8_t *alive /* n, or NULL: all */, double margin /* the reference's 5.0 m */,
+                     uint8_t *keep /* n */, double *thr /* n_pairs, may be NULL */, int64_t *n_kept /* n_pairs, may be NULL */,
+                     int32_t device, float *kernel_ms);
+/* satba_keypoints_utm is ref:feature_tracks/ft_match.py:190-217 (`keypoints_to_utm_coords`) for all images of a call, in two
+ * launches with a lane per row.  Per image c: the n_kp rows of features[c] (host, n_rows[c] x 132 float32) whose column is not NaN
+ * are taken to lead the array, as the reference takes them; their (col + col0, row + row0) are localised at alt[c] through the
+ * image's RPC record (the function satba_rpc_localization runs) and (lon, lat) are projected into the image's UTM zone by the
+ * Krueger series to n^4 (k0 = 0.9996, false easting 500 000 m, southern northings negative; csrc/satba_utm_geom.h).  zone[c]:
+ * 1..60, or 0 for the zone of the image's first keypoint (floor((lon + 180) / 6) mod 60 + 1), the reference's choice.  The rows
+ * behind the first n_kp pass their two columns through, widened, to both outputs: NaN padding stays NaN.
+ * Outputs (host, per image n_rows[c] x 2): utm_out = (easting, northing); lonlat_out (may be NULL) = (lon, lat) in degrees.
+ * SATBA_E_ARG: a negative count, NULL arrays, a non-finite RPC record, offset or altitude, a zone outside 0..60, 2^31 rows or more. */
+int satba_keypoints_utm(int32_t n_cam, const double *tables /* n_cam RPC records */, const int64_t *n_rows,
+                        const float *const *features /* per image n_rows[c] x 132 */, const double *col0row0 /* n_cam x 2 */,
+                        const double *alt /* n_cam */, const int32_t *zone /* n_cam; 0: zone of the image's first keypoint */,
+                        double *const *utm_out /* per image n_rows[c] x 2 */, double *const *lonlat_out /* same shape, or NULL */,
+                        int32_t device, float *kernel_ms);
+
 /* ---- inspection entry points (parity tests; not used by the solver loop) */
 /* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64): n must equal satba_layout_len */
 enum { SATBA_LAY_PERM = 0, SATBA_LAY_RANK, SATBA_LAY_PT_CNT, SATBA_LAY_SLICE_BASE, SATBA_LAY_E_CAM, SATBA_LAY_OBS_POS, SATBA_LAY_CAM_OFS,

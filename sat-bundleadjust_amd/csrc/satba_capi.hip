@@ -35,6 +35,7 @@
 #include "satba_camapprox.h"
 #include "satba_fundamental.h"
 #include "satba_ransac.h"
+#include "satba_utm.h"
 #include "satba_schur.h"
 #include "satba_schur_items.h"
 #include "satba_diag_split.h"
@@ -1737,6 +1738,7 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_camapprox_api.inc"
 #include "satba_fundamental_api.inc"
 #include "satba_ransac_api.inc"
+#include "satba_utm_api.inc"
 #include "satba_tracks_api.inc"
 #include "satba_ftracks_api.inc"
 #include "satba_match_api.inc"

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "satba_elbow.h"
+
 namespace satba {
 
 // err[pos] = | |f / w| |_2 of the residual pair (ref:bundle_adjust/ba_core.py:335-349), ELL order
@@ -38,11 +40,7 @@ __global__ void k_out_scatter_ell(long long K, const int* __restrict__ obs_pos, 
 //   thr = success ? max(elbow, min_thr) : v[n - 1];  cam_thr = round(thr, 2)
 __global__ __launch_bounds__(256) void k_out_elbow(const int* __restrict__ cam_ofs, const double* __restrict__ sorted, double predef_thr,
                                                    double min_thr, double* __restrict__ cam_thr) {
-    // no contraction: the removed set is index-exact only if every product and sum rounds where numpy's does.  HIP's __dmul_rn /
-    // __dadd_rn / __dsub_rn are inline functions around the plain operators and carry the translation unit's default
-    // (-ffp-contract=fast), so the compiler fused their products into the sums that follow -- the kernel was written with them until the
-    // plateau vectors of tests/cases_outliers.py (maxima that only rounding tells apart) and the two-point camera showed another argmax
-    // than numpy's.  The operators below are written out under the pragma, like k_out_err_ell's.
+    // no contraction (satba_elbow.h says why); the rounding to two decimals below is written out under the pragma too
 #pragma clang fp contract(off)
     const int cam = blockIdx.x;
     if (predef_thr >= 0.0) {
@@ -55,55 +53,9 @@ __global__ __launch_bounds__(256) void k_out_elbow(const int* __restrict__ cam_o
         if (threadIdx.x == 0) cam_thr[cam] = 0.0;
         return;
     }
-    // chord from (0, v0) to (n - 1, v_last), normalised (numpy: line_vec / sqrt(sum(line_vec ** 2)))
-    const double lx = (double)(n - 1), ly = v[n - 1] - v[0];
-    const double lxx = lx * lx, lyy = ly * ly;
-    const double nrm = __dsqrt_rn(lxx + lyy);
-    const double ux = __ddiv_rn(lx, nrm), uy = __ddiv_rn(ly, nrm);
-    double best = -1.0;
-    int best_i = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const double px = (double)i, py = v[i] - v[0];
-        const double pxu = px * ux, pyu = py * uy;
-        const double sp = pxu + pyu;
-        const double spx = sp * ux, spy = sp * uy;
-        const double qx = px - spx, qy = py - spy;
-        const double qxx = qx * qx, qyy = qy * qy;
-        const double d = __dsqrt_rn(qxx + qyy);
-        if (d > best) { best = d; best_i = i; }  // ascending i per thread: the first maximum of the thread's subset
-    }
-    __shared__ double s_d[256];
-    __shared__ int s_i[256];
-    s_d[threadIdx.x] = best; s_i[threadIdx.x] = best_i;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            const double d2 = s_d[threadIdx.x + s];
-            const int i2 = s_i[threadIdx.x + s];
-            if (d2 > s_d[threadIdx.x] || (d2 == s_d[threadIdx.x] && i2 < s_i[threadIdx.x])) { s_d[threadIdx.x] = d2; s_i[threadIdx.x] = i2; }
-        }
-        __syncthreads();
-    }
+    const Elbow e = elbow_block<256>(v, n);  // (satba_elbow.h: shared with the UTM filter, which applies another last step)
     if (threadIdx.x == 0) {
-        int arg = s_i[0];
-        if (!(s_d[0] >= 0.0) || arg >= n) arg = 0;  // n == 1: the chord is a point and numpy's distances are NaN -> argmax 0
-        const double elbow = v[arg];
-        // np.percentile(err, 80), linear interpolation with numpy's two-sided lerp.  Virtual index: method "linear" of numpy 2.2
-        // (numpy/lib/_function_base_impl.py, _QuantileMethods["linear"]: get_virtual_index = (n - 1) * quantiles, NOT the generic
-        // n q + (alpha + q (1 - alpha - beta)) - 1 of the other methods); checked bit for bit against np.percentile for n < 3000
-        // in tests/test_host_logic.py
-        const double vi = (double)(n - 1) * 0.8;
-        const int lo = (int)floor(vi), hi = min(lo + 1, n - 1);
-        const double t = vi - (double)lo, a = v[lo], bb = v[hi], diff = bb - a;
-        const double dt = diff * t;
-        double pct = a + dt;
-        if (t >= 0.5) {
-            const double t1 = 1.0 - t;
-            const double d1 = diff * t1;
-            pct = bb - d1;
-        }
-        const bool success = !(elbow < pct);
-        const double thr = success ? fmax(elbow, min_thr) : v[n - 1];
+        const double thr = e.success ? fmax(e.elbow, min_thr) : e.last;
         cam_thr[cam] = __ddiv_rn(rint(thr * 100.0), 100.0);  // np.round(thr, 2)
     }
 }

@@ -36,6 +36,7 @@ SYMBOLS = [
     "satba_rpc_affine_approx", "satba_rpc_perspective_approx", "satba_camera_resection", "satba_rpc_mesh",
     "satba_rpc_fundamental", "satba_rpc_fundamental_kernel_ms",
     "satba_ransac_fundamental", "satba_ransac_models",
+    "satba_utm_filter", "satba_keypoints_utm",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
     "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
     "satba_match_pairs", "satba_matches_fetch", "satba_matches_destroy",
@@ -162,6 +163,10 @@ def load_library(path=None):
     lib.satba_ransac_fundamental.argtypes = [C.c_int32, C.POINTER(C.c_int64), _dp, C.c_double, C.c_int32, C.c_uint64, C.POINTER(C.c_uint8), _dp, _ip,
                                              C.c_int32, C.POINTER(C.c_float)]
     lib.satba_ransac_models.argtypes = [C.c_int64, _dp, C.c_int32, _ip, _ip, _dp, C.c_int32]
+    lib.satba_utm_filter.argtypes = [C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint8), C.c_double, C.POINTER(C.c_uint8), _dp,
+                                     C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_float)]
+    lib.satba_keypoints_utm.argtypes = [C.c_int32, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _dp, _dp, _ip, C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_float)]
     _fp = C.POINTER(C.c_float)
     lib.satba_triangulate_pairwise.argtypes = [C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _dp, _fp, C.c_int32, _fp]
     lib.satba_init_pts3d.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, C.c_int32, _ip, _fp, _ip,

@@ -8,6 +8,13 @@ ref:3rdparty/sift/simd/sift4ctypes.cpp:125-195, bit for bit on integer descripto
 and its UTM consistency filter.  All pairs go to the device in one call; there is no CPU fallback: without libsatba_hip.so or
 without a GPU the calls raise.
 
+The geographic side runs on the device too.  `keypoints_to_utm_coords_batch` gives the UTM coordinates of the
+keypoints of all images in one call (satba_keypoints_utm: RPC localisation, then the Krueger series of csrc/satba_utm_geom.h).
+`utm_filter` is the UTM consistency filter of all pairs in one call (satba_utm_filter), index-exact against
+`filter_matches_inconsistent_utm_coords`; `match_stereo_pairs` renames all matches in one vectorised step and hands the geometric
+mask to that call.  The single-image `keypoints_to_utm_coords` and the per-pair `filter_matches_inconsistent_utm_coords` are kept
+as the host restatements.
+
 The fundamental matrices of "epipolar_based" matching come from `fundamental_matrices` (satba/rpc_utils.py, re-exported here): one
 matrix per pair from the two RPCs, all pairs in one device call.
 
@@ -34,10 +41,12 @@ from . import engine_hip as E
 from . import geo_utils
 from .ba_outliers import get_elbow_value
 from .ft_triangulate import _device
+from .rpc_model import rpc_to_table
 from .rpc_utils import affine_fundamental_matrix, fundamental_matrices, matches_from_rpc  # noqa: F401  (the pairs' matrices: the step in front)
 
 _lp = ct.POINTER(ct.c_int64)
 _fp = ct.POINTER(ct.c_float)
+_bp = ct.POINTER(ct.c_uint8)
 EPIPOLAR_THR = 20.0  # ref:ft_s2p.py:145
 METHODS = ("epipolar_based", "bruteforce")
 
@@ -330,34 +339,126 @@ def _check_filter(geometric_filter):
         raise ValueError('geometric_filter must be None, "ransac" or a callable, got {!r}'.format(geometric_filter))
 
 
-def _rename(m_ij, maps, canonical):
-    if m_ij.shape[0] and canonical:
-        m_ij = np.stack([maps[0][m_ij[:, 0]], maps[1][m_ij[:, 1]]], axis=1)
-    return m_ij
+def utm_filter(pair_ofs, utm4, alive=None, margin=5.0, device=None, return_info=False):
+    """
+    satba_utm_filter (include/satba.h): `filter_matches_inconsistent_utm_coords` for the matches of all pairs in one device call.
+    utm4: rows (east_i, north_i, east_j, north_j) of the matches' two keypoints, pair p being rows pair_ofs[p] : pair_ofs[p + 1];
+    alive: None or a mask of the matches that take part (a geometric filter's), the others are dropped.  Returns the boolean mask of
+    the matches kept; with return_info also a dict: thr (n_pairs; NaN where no match is alive), n_kept (n_pairs), kernel_ms.
+    """
+    pair_ofs = np.ascontiguousarray(np.asarray(pair_ofs, dtype=np.int64).reshape(-1))
+    utm4 = np.ascontiguousarray(np.asarray(utm4, dtype=np.float64).reshape(-1, 4))
+    n = utm4.shape[0]
+    if pair_ofs.size < 1 or pair_ofs[-1] != n:
+        raise ValueError("pair_ofs must hold n_pairs + 1 offsets that end at the number of matches ({}), got {}".format(n, pair_ofs[-1:]))
+    if alive is not None:
+        alive = np.ascontiguousarray(np.asarray(alive).reshape(-1) != 0, dtype=np.uint8)
+        if alive.size != n:
+            raise ValueError("alive must hold one entry per match ({}), got {}".format(n, alive.size))
+    n_pairs = pair_ofs.size - 1
+    keep = np.zeros(n, dtype=np.uint8)
+    thr, n_kept = np.full(n_pairs, np.nan), np.zeros(n_pairs, dtype=np.int64)
+    lib = E.load_library()
+    ms = ct.c_float(0.0)
+    E._check(lib, lib.satba_utm_filter(n_pairs, pair_ofs.ctypes.data_as(_lp), E._ptr(utm4), alive.ctypes.data_as(_bp) if alive is not None else None,
+                                       float(margin), keep.ctypes.data_as(_bp), E._ptr(thr), n_kept.ctypes.data_as(_lp), _device(device), ct.byref(ms)))
+    keep = keep.astype(bool)
+    if return_info:
+        return keep, {"thr": thr, "n_kept": n_kept, "kernel_ms": ms.value}
+    return keep
 
 
-def _ransac_masks(jobs, tracks_config, seed, device):
-    """the masks of all pairs (jobs: (m_ij, feats_i, feats_j) per pair, renamed) from one device call, and its kernel time"""
-    ofs = np.cumsum([0] + [m_ij.shape[0] for m_ij, _, _ in jobs]).astype(np.int64)
-    if ofs[-1] == 0:
-        return [np.zeros(0, dtype=bool) for _ in jobs], 0.0
-    xy = np.concatenate([_match_coords(fi, fj, m_ij) for m_ij, fi, fj in jobs if m_ij.shape[0]], axis=0)
-    mask, info = ransac_fundamental(ofs, xy, max_err=tracks_config.get("FT_ransac", 0.3), seed=seed, device=device, return_info=True)
-    return [mask[ofs[k]:ofs[k + 1]] for k in range(len(jobs))], info["kernel_ms"]
+def keypoints_to_utm_coords_batch(features, rpcs, offsets, alts, zone=None, device=None, return_lonlat=False, return_info=False):
+    """
+    satba_keypoints_utm (include/satba.h): `keypoints_to_utm_coords` for all images in one device call.  features: per image an
+    (n, 132) array or .npy path; rpcs: per image an RPC model; offsets: per image a dict with "col0" and "row0"; alts: one altitude
+    for all images or one per image.  zone=None takes, per image, the zone of its first keypoint, as the reference does; an integer
+    1..60 makes all images share that zone (a sequence gives one per image).  Returns the list of (n, 2) arrays (easting, northing),
+    the NaN padding of the features kept; with return_lonlat also the list of (n, 2) arrays (lon, lat) the localisation gave; with
+    return_info also a dict: kernel_ms.
+    """
+    feats = [_load(f, np.float32, 132) for f in features]
+    n_cam = len(feats)
+    if len(rpcs) != n_cam or len(offsets) != n_cam:
+        raise ValueError("features, rpcs and offsets must list the same images")
+    tables = np.ascontiguousarray(np.array([rpc_to_table(r) for r in rpcs], dtype=np.float64).reshape(n_cam, 90))
+    off = np.ascontiguousarray(np.array([[o["col0"], o["row0"]] for o in offsets], dtype=np.float64).reshape(n_cam, 2))
+    alts = np.ascontiguousarray(np.broadcast_to(np.asarray(alts, dtype=np.float64), (n_cam,)))
+    if zone is None:
+        zones = np.zeros(n_cam, dtype=np.int32)
+    else:
+        zones = np.ascontiguousarray(np.broadcast_to(np.asarray(zone, dtype=np.int32), (n_cam,)))
+        if n_cam and (zones.min() < 1 or zones.max() > 60):
+            raise ValueError("a UTM zone lies in 1..60, got {!r}".format(zone))
+    n_rows = np.array([f.shape[0] for f in feats], dtype=np.int64)
+    utm = [np.zeros((f.shape[0], 2), dtype=np.float64) for f in feats]
+    lonlat = [np.zeros((f.shape[0], 2), dtype=np.float64) for f in feats] if return_lonlat else None
+    fptr = (ct.c_void_p * n_cam)(*[a.ctypes.data for a in feats])
+    uptr = (ct.c_void_p * n_cam)(*[a.ctypes.data for a in utm])
+    lptr = (ct.c_void_p * n_cam)(*[a.ctypes.data for a in lonlat]) if return_lonlat else None
+    lib = E.load_library()
+    ms = ct.c_float(0.0)
+    E._check(lib, lib.satba_keypoints_utm(n_cam, E._ptr(tables), n_rows.ctypes.data_as(_lp), fptr, E._ptr(off), E._ptr(alts), E._ptr(zones, E._ip), uptr,
+                                          lptr, _device(device), ct.byref(ms)))
+    out = (utm,) + ((lonlat,) if return_lonlat else ()) + (({"kernel_ms": ms.value},) if return_info else ())
+    return out if len(out) > 1 else utm
 
 
-def _after_match(m_ij, feats_i, feats_j, utm_i, utm_j, geometric_filter, mask=None):
-    """the geometric filter (a callable, or the mask the device RANSAC gave) and the UTM filter of one renamed pair on the host"""
-    n = [m_ij.shape[0]]
-    if m_ij.shape[0] and geometric_filter is not None:
-        if mask is None:
-            mask = geometric_filter(np.asarray(feats_i[:, :2]), np.asarray(feats_j[:, :2]), m_ij)
-        m_ij = m_ij[np.asarray(mask, dtype=bool).reshape(-1)]
-        n.append(m_ij.shape[0])
-    if m_ij.shape[0]:
-        m_ij = filter_matches_inconsistent_utm_coords(m_ij, utm_i, utm_j)
-    n.append(m_ij.shape[0])
-    return m_ij, n
+def _rename_all(ofs, kp_i, kp_j, sides, feats, canonical):
+    """
+    The renaming of the matches of all pairs in one vectorised step (sides: the two images of every pair; the matches of pair p are
+    rows ofs[p] : ofs[p + 1]; host only).  Returns m_ij (n, 2) renamed through the images' index maps, im (n, 2) the images of every
+    match, `used` the images in use, ascending, and `rows` (n, 2): where the two keypoints of a match stand when the arrays of the
+    images in use are put behind one another.
+    """
+    sides = np.asarray(sides, dtype=np.int64).reshape(-1, 2)
+    im = sides[np.repeat(np.arange(len(sides)), np.diff(ofs))]
+    m_ij = np.stack([kp_i, kp_j], axis=1).astype(np.int64)
+    used = np.unique(sides)
+    base = np.zeros(len(feats) + 1, dtype=np.int64)
+    base[used + 1] = [feats[c].shape[0] for c in used]
+    base = np.cumsum(base)[:-1]
+    rows = m_ij + base[im]
+    if canonical and m_ij.shape[0]:
+        rows = np.concatenate([canonical_index_map(feats[c]) + base[c] for c in used])[rows]
+        m_ij = rows - base[im]
+    return m_ij, im, used, rows
+
+
+def _both_sides(arrays, used, rows):
+    """(n, 2 k): the rows of the two keypoints of every match out of per-image (n_kp, k) arrays"""
+    a = np.concatenate([np.asarray(arrays[c]) for c in used], axis=0)
+    return np.concatenate([a[rows[:, 0]], a[rows[:, 1]]], axis=1)
+
+
+def _rename_and_filter(ofs, kp_i, kp_j, sides, feats, utms, canonical, geometric_filter, tracks_config, ransac_seed, device):
+    """
+    What follows the device match, for all pairs at once: the renaming (`_rename_all`), the geometric filter ("ransac": one device
+    call; a callable: called once per pair that has matches, in order) and the UTM filter (one device call, the geometric mask as
+    its `alive`).  Returns m_ij (n, 2) renamed, im (n, 2), alive (n, bool; None without a geometric filter), keep (n, bool) and the
+    kernel times.
+    """
+    m_ij, im, used, rows = _rename_all(ofs, kp_i, kp_j, sides, feats, canonical)
+    n = m_ij.shape[0]
+    info = {"utm_kernel_ms": 0.0}
+    if geometric_filter == "ransac":
+        info["ransac_kernel_ms"] = 0.0
+    if n == 0:
+        return m_ij, im, (None if geometric_filter is None else np.zeros(0, dtype=bool)), np.zeros(0, dtype=bool), info
+    alive = None
+    if geometric_filter == "ransac":
+        xy = _both_sides([f[:, :2] if f is not None else None for f in feats], used, rows).astype(np.float64)
+        alive, rinfo = ransac_fundamental(ofs, xy, max_err=tracks_config.get("FT_ransac", 0.3), seed=ransac_seed, device=device, return_info=True)
+        info["ransac_kernel_ms"] = rinfo["kernel_ms"]
+    elif geometric_filter is not None:
+        alive = np.zeros(n, dtype=bool)
+        for p, (i, j) in enumerate(np.asarray(sides, dtype=np.int64).reshape(-1, 2)):
+            if ofs[p + 1] > ofs[p]:
+                mask = geometric_filter(np.asarray(feats[i][:, :2]), np.asarray(feats[j][:, :2]), m_ij[ofs[p]:ofs[p + 1]])
+                alive[ofs[p]:ofs[p + 1]] = np.asarray(mask, dtype=bool).reshape(-1)
+    keep, uinfo = utm_filter(ofs, _both_sides(utms, used, rows), alive, device=device, return_info=True)
+    info["utm_kernel_ms"] = uinfo["kernel_ms"]
+    return m_ij, im, alive, keep, info
 
 
 def _polygon_box(utm_polygon):
@@ -385,10 +486,13 @@ def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygo
                                         return_info=True)
     if info["n_empty_pairs"]:
         return None, [0, 0, 0]
-    maps = (canonical_index_map(fi), canonical_index_map(fj)) if canonical else None
-    m_ij = _rename(np.stack([kp_i, kp_j], axis=1).astype(np.int64), maps, canonical)
-    mask = _ransac_masks([(m_ij, fi, fj)], tracks_config, ransac_seed, device)[0][0] if geometric_filter == "ransac" else None
-    m_ij, n = _after_match(m_ij, fi, fj, ui, uj, geometric_filter, mask)
+    m_ij, _, alive, keep, _ = _rename_and_filter(ofs, kp_i, kp_j, [(0, 1)], [fi, fj], [ui, uj], canonical, geometric_filter, tracks_config, ransac_seed,
+                                                 device)
+    n = [m_ij.shape[0]]
+    if m_ij.shape[0] and alive is not None:
+        n.append(int(alive.sum()))
+    n.append(int(keep.sum()))
+    m_ij = m_ij[keep]
     return (m_ij if m_ij.shape[0] else None), n
 
 
@@ -399,7 +503,8 @@ def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_
     "geojson" polygon in UTM coordinates (convex).  F: per pair a 3 x 3 fundamental matrix ("epipolar_based").  Returns the M x 4
     int64 array (kp_i, kp_j, im_i, im_j), pairs in the given order; a pair whose footprints share no area gives no rows.
     geometric_filter: None, a callable per pair, or "ransac": the device RANSAC over all pairs in one call (module docstring), whose
-    kernel time return_info reports as "ransac_kernel_ms".
+    kernel time return_info reports as "ransac_kernel_ms".  The renaming and the UTM filter take all pairs at once; the filter is one
+    device call (`utm_filter`), whose kernel time return_info reports as "utm_kernel_ms".
     """
     method = _method(tracks_config)
     _check_filter(geometric_filter)
@@ -410,6 +515,7 @@ def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_
     live = [k for k, b in enumerate(boxes) if b is not None]
     out = np.zeros((0, 4), dtype=np.int64)
     info = {"n_selected": 0, "n_empty_pairs": 0, "path": "int8", "kernel_ms": 0.0}
+    times = {"utm_kernel_ms": 0.0}
     if live:
         Fs = [F[k] for k in live] if method == "epipolar_based" else None
         used = set(c for k in live for c in pairs[k])
@@ -419,21 +525,8 @@ def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_
         utms = [_load(utm_coords[c], np.float64, 2) if c in used else None for c in range(len(utm_coords))]
         ofs, kp_i, kp_j, info = match_pairs([pairs[k] for k in live], feats, utms, [boxes[k] for k in live], F=Fs,
                                             thr=tracks_config.get("FT_rel_thr", 0.6), device=device, return_info=True)
-        maps = {c: canonical_index_map(feats[c]) for c in used} if canonical else None
-        jobs = []
-        for m, k in enumerate(live):
-            i, j = pairs[k]
-            m_ij = np.stack([kp_i[ofs[m]:ofs[m + 1]], kp_j[ofs[m]:ofs[m + 1]]], axis=1).astype(np.int64)
-            jobs.append((_rename(m_ij, (maps[i], maps[j]) if canonical else None, canonical), feats[i], feats[j]))
-        masks = [None] * len(jobs)
-        if geometric_filter == "ransac":
-            masks, info["ransac_kernel_ms"] = _ransac_masks(jobs, tracks_config, ransac_seed, device)
-        rows = []
-        for (m_ij, _, _), mask, k in zip(jobs, masks, live):
-            i, j = pairs[k]
-            m_ij, _ = _after_match(m_ij, feats[i], feats[j], utms[i], utms[j], geometric_filter, mask)
-            if m_ij.shape[0]:
-                rows.append(np.concatenate([m_ij, np.tile(np.array([[i, j]], dtype=np.int64), (m_ij.shape[0], 1))], axis=1))
-        if rows:
-            out = np.concatenate(rows, axis=0)
+        m_ij, im, _, keep, times = _rename_and_filter(ofs, kp_i, kp_j, [pairs[k] for k in live], feats, utms, canonical, geometric_filter, tracks_config,
+                                                      ransac_seed, device)
+        out = np.concatenate([m_ij, im], axis=1)[keep]
+    info.update(times)
     return (out, info) if return_info else out

@@ -2,8 +2,10 @@
 WGS-84 geocentric <-> geodetic conversions used inside every RPC residual
 (ref:bundle_adjust/geo_utils.py:218-255).  Host (numpy) versions; the device version of
 `ecef_to_latlon_custom` and its 3x3 Jacobian live in csrc/satba_models.h (`geodetic<JAC>`).
-The UTM helpers serve the figure functions of satba/ba_core.py only (ref:bundle_adjust/geo_utils.py:15-97 does the
-same through pyproj / utm, which are not dependencies of this package).
+The UTM helpers serve the figure functions of satba/ba_core.py and the single-image `ft_match.keypoints_to_utm_coords`
+(ref:bundle_adjust/geo_utils.py:15-97 does the same through pyproj / utm, which are not dependencies of this package).  The
+device version of `utm_from_lonlat`, the same series term for term, is csrc/satba_utm_geom.h behind
+`ft_match.keypoints_to_utm_coords_batch`; this one is the restatement its tests compare against.
 """
 import numpy as np
 
@@ -39,7 +41,7 @@ def ecef_to_latlon_custom(x, y, z):
     return np.rad2deg(lat), np.rad2deg(lon), alt
 
 
-# ----------------------------------------------------------------------------- UTM (figures only)
+# ----------------------------------------------------------------------------- UTM (host restatement of csrc/satba_utm_geom.h)
 
 def utm_zone_from_lonlat(lon, lat):
     """Zone number of the standard 6-degree UTM grid (no Norway / Svalbard exceptions)."""
