@@ -618,14 +618,18 @@ int satba_keypoints_utm(int32_t n_cam, const double *tables /* n_cam RPC records
                         int32_t device, float *kernel_ms);
 
 /* ---- inspection entry points (parity tests; not used by the solver loop) */
-/* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64): n must equal satba_layout_len */
+/* index structures built by satba_problem_create, as int32 arrays (SATBA_LAY_PAIR_OFS: int64, SATBA_LAY_E_CAM8: uint8): n must equal
+ * satba_layout_len */
 enum { SATBA_LAY_PERM = 0, SATBA_LAY_RANK, SATBA_LAY_PT_CNT, SATBA_LAY_SLICE_BASE, SATBA_LAY_E_CAM, SATBA_LAY_OBS_POS, SATBA_LAY_CAM_OFS,
        SATBA_LAY_CM_PT, SATBA_LAY_CM_POS, SATBA_LAY_PAIR_OFS, SATBA_LAY_PAIR_PTS, SATBA_LAY_PAIR_PI, SATBA_LAY_PAIR_PJ, SATBA_LAY_PAIR_IJ, SATBA_LAY_CM_IO, SATBA_LAY_IPT_OFS,
        /* the merged records of the weighted / robust runs (affine, perspective; built by the first such linearisation, length -1 before):
         * piece offsets of the records' fixed parts (n_pts + 1: the last one is the all-zero record), of every point's first row scale,
         * the pair lists as (record, distances of the two scales in front of it), the camera-major lists as (record, scale piece), the
         * first camera-major entry of every diagonal item (+ 1 sentinel) */
-       SATBA_LAY_W_FIX, SATBA_LAY_SC_OFS, SATBA_LAY_PAIR_REC, SATBA_LAY_PAIR_KK, SATBA_LAY_CM_REC, SATBA_LAY_CM_SC, SATBA_LAY_DG_OFS };
+       SATBA_LAY_W_FIX, SATBA_LAY_SC_OFS, SATBA_LAY_PAIR_REC, SATBA_LAY_PAIR_KK, SATBA_LAY_CM_REC, SATBA_LAY_CM_SC, SATBA_LAY_DG_OFS,
+       /* the cameras of the ELL slots in one byte each (padding 0xFF), which the point kernels stream when there are at most 255 cameras
+        * and SATBA_CAM_NARROW is not 0; length -1 where it is not built */
+       SATBA_LAY_E_CAM8 };
 int64_t satba_layout_len(const satba_problem *p, int32_t which);
 int satba_get_layout(satba_problem *p, int32_t which, int64_t n, void *host_out);
 /* n >= 16 doubles: [0..4] milliseconds since the start of satba_problem_create when the uploads were queued, the layout sizes were
@@ -639,7 +643,8 @@ int satba_get_layout(satba_problem *p, int32_t which, int64_t n, void *host_out)
  * chunk) of the weighted / robust pair kernel, 0 before the merged records exist (n >= 20), [20] log2 of the lanes per point
  * that the next launch of the point kernels uses with the loss configured now (n >= 21), [21] log2 of the replicas of
  * k_linearize's camera-sum table in LDS (n >= 22), [22] the first camera whose diagonal block and right-hand-side entries the
- * last Schur front produced BEHIND its pair kernel (csrc/satba_diag_split.h; the number of cameras: none; -1: no front yet) (n >= 23) */
+ * last Schur front produced BEHIND its pair kernel (csrc/satba_diag_split.h; the number of cameras: none; -1: no front yet) (n >= 23),
+ * [23] the point kernels read the camera of an ELL slot from the one-byte array SATBA_LAY_E_CAM8 (1) or from SATBA_LAY_E_CAM (0) (n >= 24) */
 int satba_get_info(const satba_problem *p, double *out, int32_t n);
 /* normal-equation blocks of the last linearize: U (M n_p n_p), g_c (M n_p) as written to the exchange
  * payload, V (N x 6: xx xy xz yy yz zz), g_p (N x 3), points in the caller's order. Any pointer may be NULL.

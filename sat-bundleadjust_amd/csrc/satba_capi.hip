@@ -101,6 +101,7 @@ struct satba_problem {
     int camc_lds = 0, rpc_lds = 0;  // per-camera tables staged in LDS by the observation kernels
     int cam_sums_lds = 1;           // k_linearize accumulates diag U_c / g_c with LDS atomics (0: camera-major pass k_cam_sums)
     int lin_rep_shift = 0;          // log2 of the replicas of that LDS table (few cameras: same-address atomics serialise)
+    int cam_narrow = 0;             // the point kernels stream the camera of a slot as one byte (Layout::e_cam8): at most 255 cameras
     int deterministic = 0;
     int split_env = -1;             // SATBA_SPLIT at satba_problem_create (experiments, tests): log2 of the lanes per point, -1 unset (slice_split)
     // fixed-point camera sums of k_linearize (satba_kernels.h): scales / bounds / inverse scales per slot, overflow flag, bounding
@@ -273,7 +274,7 @@ static bool pairs_run(const satba_problem* p) { return p->L.n_pairs > 0 && p->L.
 static ObsArgs obs_args(const satba_problem* p, bool at_new, const int* gate = nullptr) {
     ObsArgs a;
     const Layout& L = p->L;
-    a.e_cam = L.e_cam; a.e_obs = L.e_obs; a.e_w = L.e_w; a.slice_base = L.slice_base; a.pt_cnt = L.pt_cnt; a.perm = L.perm;
+    a.e_cam = L.e_cam; a.e_cam8 = L.e_cam8; a.e_obs = L.e_obs; a.e_w = L.e_w; a.slice_base = L.slice_base; a.pt_cnt = L.pt_cnt; a.perm = L.perm;
     a.ipt_ofs = L.ipt_ofs;
     a.x = at_new ? p->d_xnew : p->d_x;
     a.camc = at_new ? p->d_camc_new : p->d_camc;
@@ -768,11 +769,15 @@ static int build_layout(satba_problem* p, const satba_problem_desc* d) {
     const size_t Pz = (size_t)std::max(L.P, 1);
     TRY(dev_alloc(p, &L.e_cam, Pz + 64)); TRY(dev_alloc(p, &L.e_obs, Pz + 64)); TRY(dev_alloc(p, &L.e_w, Pz + 64));
     HIP_TRY(hipMemsetAsync(L.e_cam, 0xFF, sizeof(int) * (Pz + 64), st));
+    if (p->cam_narrow) {  // the one-byte camera stream of the point kernels (Layout::e_cam8)
+        TRY(dev_alloc(p, &L.e_cam8, Pz + 64));
+        HIP_TRY(hipMemsetAsync(L.e_cam8, 0xFF, Pz + 64, st));
+    }
     HIP_TRY(hipMemsetAsync(L.e_obs, 0, sizeof(double2) * (Pz + 64), st));
     HIP_TRY(hipMemsetAsync(L.e_w, 0, sizeof(double) * (Pz + 64), st));
     if (K) {
         hipLaunchKernelGGL(k_lay_fill_ell, dim3(grid_for(K, 256, 8192)), dim3(256), 0, st, K, o_cam, L.pts_ind, o_obs, o_w, o_ofs, L.rank,
-                           L.slice_base, ipt_ofs, L.e_cam, L.e_obs, L.e_w, L.obs_pos, io_cam, io_pos, io_pt);
+                           L.slice_base, ipt_ofs, L.e_cam, L.e_cam8, L.e_obs, L.e_w, L.obs_pos, io_cam, io_pos, io_pt);
         // camera-major lists: stable sort of the internal point-major list by camera
         hipLaunchKernelGGL(k_lay_iota, dim3(grid_for(K, 256, 4096)), dim3(256), 0, st, K, io_iota);
         need = cub_bytes;
@@ -882,6 +887,8 @@ int satba_problem_create(const satba_problem_desc* d, satba_problem** out) {
     p->lead = p->rank == 0 ? 1.0 : 0.0;
     p->deterministic = ((d->flags & SATBA_FLAG_DETERMINISTIC) || getenv("SATBA_DETERMINISTIC")) ? 1 : 0;
     if (const char* ss = getenv("SATBA_SPLIT")) p->split_env = atoi(ss);  // experiments, tests (negative: the rule, as unset)
+    const char* cn = getenv("SATBA_CAM_NARROW");  // A/B runs, tests: 0 keeps the int stream
+    p->cam_narrow = (p->M <= 255 && !(cn && atoi(cn) == 0)) ? 1 : 0;  // (0xFF, the padding, is then no camera)
 
     int rc = [&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
@@ -1624,6 +1631,7 @@ int64_t satba_layout_len(const satba_problem* p, int32_t which) {
         case SATBA_LAY_PERM: case SATBA_LAY_RANK: case SATBA_LAY_PT_CNT: return L.N;
         case SATBA_LAY_SLICE_BASE: return L.n_slices + 1;
         case SATBA_LAY_E_CAM: return L.P;
+        case SATBA_LAY_E_CAM8: return L.e_cam8 ? L.P : -1;
         case SATBA_LAY_OBS_POS: case SATBA_LAY_CM_PT: case SATBA_LAY_CM_POS: case SATBA_LAY_CM_IO: return L.K;
         case SATBA_LAY_IPT_OFS: return L.N + 1;
         case SATBA_LAY_CAM_OFS: return L.M + 1;
@@ -1651,6 +1659,7 @@ int satba_get_layout(satba_problem* p, int32_t which, int64_t n, void* host_out)
         case SATBA_LAY_PT_CNT: src = L.pt_cnt; break;
         case SATBA_LAY_SLICE_BASE: src = L.slice_base; break;
         case SATBA_LAY_E_CAM: src = L.e_cam; break;
+        case SATBA_LAY_E_CAM8: src = L.e_cam8; esz = 1; break;
         case SATBA_LAY_OBS_POS: src = L.obs_pos; break;
         case SATBA_LAY_CM_PT: src = L.cm_pt; break;
         case SATBA_LAY_CM_POS: src = L.cm_pos; break;
@@ -1690,6 +1699,7 @@ int satba_get_info(const satba_problem* p, double* out, int32_t n) {
     if (n > 20) out[20] = slice_split(p);
     if (n > 21) out[21] = p->lin_rep_shift;
     if (n > 22) out[22] = p->diag_split_last;
+    if (n > 23) out[23] = p->cam_narrow;
     return 0;
 }
 

@@ -107,6 +107,8 @@ struct ObsArgs {
     double* prep_ghs;                    // g_h / scale_inv       themselves from g and scale_inv, which they read anyway: point_gh below)
     const int* prep_first_dev;           // first linearisation of a solve (device-resident loop), else prep_first
     int prep_first;
+    const unsigned char* __restrict__ e_cam8;  // P: e_cam in one byte (0xFF: padding), what the slice walks stream; null: more than 255
+                                               // cameras (or SATBA_CAM_NARROW=0) -- they read e_cam (CamStream below)
 };
 
 // deterministic grid-wide sums: every workgroup writes its partial, the last one to arrive adds them up in index order
@@ -210,6 +212,26 @@ struct ObsEval {
     }
 };
 
+// Camera of an ELL slot for the kernels that walk the slices: one byte from e_cam8 where the layout has it (4 -> 1 byte per observation
+// and pass: 30 MB of 10 M observations), else the int of e_cam.  Which one is a kernel argument, the same for every wave of every launch on
+// a handle, so it is taken ONCE per kernel -- base and log2 of the slot size in SGPRs -- and a slot costs one address (pos << shift)
+// and a scalar branch round ONE load of that width: neither a second load nor a select.  Padding slots (0xFF / -1) are not read by
+// these kernels (slot < pt_cnt).  narrow = false (a compile-time choice of the caller): e_cam whatever the layout has, and no branch.
+struct CamStream {
+    const unsigned char* base;
+    int shift;
+    __device__ inline explicit CamStream(const ObsArgs& a, bool narrow = true)
+        : base(narrow && a.e_cam8 ? a.e_cam8 : reinterpret_cast<const unsigned char*>(a.e_cam)), shift(narrow && a.e_cam8 ? 0 : 2) {}
+    __device__ inline int operator()(int pos) const {
+        const unsigned char* p = base + ((size_t)pos << shift);
+        return shift ? *reinterpret_cast<const int*>(p) : (int)*p;
+    }
+};
+// Fixed-point mask of internal point q (0: the caller's point perm[q] is one of the first n_pts_fix, which stay where they are).
+// Without fixed points -- the usual case -- perm is not read: 4 bytes per point and pass (skip = false: it is read regardless).
+__device__ inline double point_mask(const int* __restrict__ perm, int n_pts_fix, int q, bool skip = true) {
+    return ((skip && n_pts_fix == 0) || perm[q] >= n_pts_fix) ? 1.0 : 0.0;
+}
 // one observation record of the ELL stream (camera, observed pixel, weight); `on` false: nothing is fetched
 #ifndef SATBA_PF
 #define SATBA_PF 2  // slots of the ELL stream in flight ahead of the one being evaluated
@@ -219,9 +241,9 @@ struct ObsRec {
     double2 ob = {0.0, 0.0};
     double w = 1.0;
     template <bool UNITW>
-    __device__ inline void load(const ObsArgs& a, int pos, bool on) {
+    __device__ inline void load(const ObsArgs& a, const CamStream& cams, int pos, bool on) {
         if (on) {
-            cam = a.e_cam[pos];
+            cam = cams(pos);
             ob = a.e_obs[pos];
             if constexpr (!UNITW) w = a.e_w[pos];
         }
@@ -486,6 +508,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_residual(ObsArgs a, double2* __
     CamTables<CL, RL> T;
     T.stage(a, s_dyn_res, RES_THREADS);
     const int lane = threadIdx.x & 63;
+    const CamStream cams(a);
     constexpr int WAVES = RES_THREADS / 64;
     double acc = 0.0, ss = 0.0, xx = 0.0;
     if (TRIAL && blockIdx.x == 0) {  // the camera entries of the two sums (x_new of the cameras is k_trial_cams' work)
@@ -520,10 +543,10 @@ __global__ __launch_bounds__(RES_THREADS) void k_residual(ObsArgs a, double2* __
         // software pipeline: the records of the next two slots are in flight during the arithmetic of the current one
         ObsRec r[SATBA_PF + 1];
 #pragma unroll
-        for (int j = 0; j < SATBA_PF; ++j) r[j].template load<UNITW>(a, pos + su.step * j, su.slot(j) < cnt);
+        for (int j = 0; j < SATBA_PF; ++j) r[j].template load<UNITW>(a, cams, pos + su.step * j, su.slot(j) < cnt);
         for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
             const int k = su.slot(tt);
-            r[SATBA_PF].load<UNITW>(a, pos + su.step * SATBA_PF, su.slot(tt + SATBA_PF) < cnt);
+            r[SATBA_PF].load<UNITW>(a, cams, pos + su.step * SATBA_PF, su.slot(tt + SATBA_PF) < cnt);
             __builtin_amdgcn_sched_barrier(0);
             if (k < cnt) {
                 ObsEval<MODEL, NP, false, !UNITW, false, UNITW> e;
@@ -632,6 +655,10 @@ __global__ __launch_bounds__(LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6
     T.stage(a, s_lin + (CAMSUMS ? cam_sum_bytes(NP, n_rows) / 8 : 0), THREADS);
     if constexpr (CAMSUMS && !CL && !RL) __syncthreads();
     const int lane = threadIdx.x & 63;
+    // The variants that spill as they are -- perspective cameras with weights or a robust loss (44 - 88 bytes at 128 VGPRs), RPC (600 -
+    // 800 at 256) -- keep the int stream and the read of perm: a uniform branch in their slot loop moved the spills by 4 - 40 bytes
+    constexpr bool LEAN = MODEL == AFFINE || (MODEL == PERSPECTIVE && UNITW && !ROBUST);
+    const CamStream cams(a, LEAN);
     const bool const_t = lin_const_t(MODEL, NP, ROBUST, a.unit != 0);
 
     double cost = 0.0, gmax = 0.0, s_gh = 0.0, s_xs = 0.0;
@@ -645,20 +672,20 @@ __global__ __launch_bounds__(LinCfg<((ROBUST && !SOFT) || MODEL == RPC || NP > 6
         if (has) {
             const double* px = a.x + a.n_c + 3 * (size_t)q;
             X = px[0]; Y = px[1]; Z = px[2];
-            mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
+            mp = point_mask(a.perm, a.n_pts_fix, q, LEAN);
         }
         double v[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         int pos = su.pos;
-        const int io0 = has ? a.ipt_ofs[q] : 0;
+        const int io0 = (has && (!LEAN || a.sc)) ? a.ipt_ofs[q] : 0;  // (LEAN: only read where it is used -- the row scales)
         // software pipeline: the records of the next two slots are in flight during the arithmetic and the LDS atomics of this one
         // (one slot for the robust variants: with two the soft_l1 kernel spilled 13 registers at its 128-VGPR limit)
         constexpr int PF = ROBUST ? 1 : SATBA_PF;
         ObsRec r[PF + 1];
 #pragma unroll
-        for (int j = 0; j < PF; ++j) r[j].template load<UNITW>(a, pos + su.step * j, su.slot(j) < cnt);
+        for (int j = 0; j < PF; ++j) r[j].template load<UNITW>(a, cams, pos + su.step * j, su.slot(j) < cnt);
         for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
             const int k = su.slot(tt);
-            r[PF].template load<UNITW>(a, pos + su.step * PF, su.slot(tt + PF) < cnt);
+            r[PF].template load<UNITW>(a, cams, pos + su.step * PF, su.slot(tt + PF) < cnt);
             __builtin_amdgcn_sched_barrier(0);
             if (k < cnt) {
                 const int cam = r[0].cam;
@@ -1228,6 +1255,7 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
     SATBA_GATE(a.gate);
     extern __shared__ __attribute__((aligned(16))) double s_dyn_jvp[];
     const int lane = threadIdx.x & 63;
+    const CamStream cams(a);
     constexpr int WAVES = JVP_THREADS / 64;
     double s11 = 0.0, s12 = 0.0, s22 = 0.0;
     if constexpr (MODEL == AFFINE && PRE && NV == 1) {
@@ -1242,12 +1270,12 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
             if (has) {
                 const size_t ip = (size_t)a.n_c + 3 * (size_t)q;
                 X = a.x[ip]; Y = a.x[ip + 1]; Z = a.x[ip + 2];
-                const double mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
+                const double mp = point_mask(a.perm, a.n_pts_fix, q);
                 if (g_pre) { v0 = mp * point_ghs(g_pre, scale_inv, ip); v1 = mp * point_ghs(g_pre, scale_inv, ip + 1); v2 = mp * point_ghs(g_pre, scale_inv, ip + 2); }
                 else { v0 = mp * q1[ip]; v1 = mp * q1[ip + 1]; v2 = mp * q1[ip + 2]; }
             }
             int pos = su.pos;
-            const int io0 = has ? a.ipt_ofs[q] : 0;
+            const int io0 = (has && a.sc) ? a.ipt_ofs[q] : 0;  // only the row scales are indexed by it
             // cameras (and row scales) of the next two slots in flight
             constexpr int D = SATBA_CAM_PF;
             int cq[D];
@@ -1256,13 +1284,13 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
             for (int d = 0; d < D; ++d) {
                 const int kd = su.slot(d);
                 cq[d] = 0; sq[d] = make_double2(1.0, 1.0);
-                if (kd < cnt) { cq[d] = a.e_cam[pos + d * su.step]; if (a.sc) sq[d] = a.sc[io0 + kd]; }
+                if (kd < cnt) { cq[d] = cams(pos + d * su.step); if (a.sc) sq[d] = a.sc[io0 + kd]; }
             }
             for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
                 const int k = su.slot(tt), kn = su.slot(tt + D);
                 int cn = 0;
                 double2 sn = make_double2(1.0, 1.0);
-                if (kn < cnt) { cn = a.e_cam[pos + D * su.step]; if (a.sc) sn = a.sc[io0 + kn]; }
+                if (kn < cnt) { cn = cams(pos + D * su.step); if (a.sc) sn = a.sc[io0 + kn]; }
                 __builtin_amdgcn_sched_barrier(0);
                 const int c0 = cq[0];
                 const double2 s0 = sq[0];
@@ -1297,7 +1325,7 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
             if (has) {
                 const size_t ip = (size_t)a.n_c + 3 * (size_t)q;
                 X = a.x[ip]; Y = a.x[ip + 1]; Z = a.x[ip + 2];
-                const double mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
+                const double mp = point_mask(a.perm, a.n_pts_fix, q);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     const double si = 1.0 / scale_inv[ip + j];
@@ -1306,7 +1334,7 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
                 }
             }
             int pos = su.pos;
-            const int io0 = has ? a.ipt_ofs[q] : 0;
+            const int io0 = (has && a.sc) ? a.ipt_ofs[q] : 0;  // only the row scales are indexed by it
             constexpr int D = SATBA_CAM_PF;
             int cq[D];
             double2 sq[D];
@@ -1314,13 +1342,13 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
             for (int d = 0; d < D; ++d) {
                 const int kd = su.slot(d);
                 cq[d] = 0; sq[d] = make_double2(1.0, 1.0);
-                if (kd < cnt) { cq[d] = a.e_cam[pos + d * su.step]; if (a.sc) sq[d] = a.sc[io0 + kd]; }
+                if (kd < cnt) { cq[d] = cams(pos + d * su.step); if (a.sc) sq[d] = a.sc[io0 + kd]; }
             }
             for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
                 const int k = su.slot(tt), kn = su.slot(tt + D);
                 int cn = 0;
                 double2 sn = make_double2(1.0, 1.0);
-                if (kn < cnt) { cn = a.e_cam[pos + D * su.step]; if (a.sc) sn = a.sc[io0 + kn]; }
+                if (kn < cnt) { cn = cams(pos + D * su.step); if (a.sc) sn = a.sc[io0 + kn]; }
                 __builtin_amdgcn_sched_barrier(0);
                 const int c0 = cq[0];
                 const double2 s0 = sq[0];
@@ -1355,7 +1383,7 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
             if (has) {
                 const size_t ip = (size_t)a.n_c + 3 * (size_t)q;
                 X = a.x[ip]; Y = a.x[ip + 1]; Z = a.x[ip + 2];
-                mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
+                mp = point_mask(a.perm, a.n_pts_fix, q);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     if constexpr (PRE) p1[j] = g_pre ? point_ghs(g_pre, scale_inv, ip + j) : q1[ip + j];
@@ -1367,11 +1395,11 @@ __global__ __launch_bounds__(JVP_THREADS) void k_jvp(ObsArgs a, const double* __
                 }
             }
             int pos = su.pos;
-            const int io0 = has ? a.ipt_ofs[q] : 0;
+            const int io0 = (has && (MODEL == RPC || a.sc)) ? a.ipt_ofs[q] : 0;  // only read where it is used: stored RPC rows, row scales
             for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
                 const int k = su.slot(tt);
                 if (k < cnt) {
-                    const int cam = a.e_cam[pos];
+                    const int cam = cams(pos);
                     ObsEval<MODEL, NP, true> e;
                     e.jac(a, io0 + k, cam, mp, T.cc(cam), T.tab(cam), X, Y, Z);
                     const size_t ic = (size_t)cam * NP;
@@ -1583,6 +1611,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
     SATBA_GATE(a.gate);
     extern __shared__ __attribute__((aligned(16))) double s_dyn_bs[];
     const int lane = threadIdx.x & 63;
+    const CamStream cams(a);
     constexpr int WAVES = BS_THREADS / 64;
     double sa = 0.0, sb = 0.0, sc = 0.0;
     if (blockIdx.x == 0) {
@@ -1605,11 +1634,11 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
         if (has) {
             const double* px = a.x + a.n_c + 3 * (size_t)q;
             X = px[0]; Y = px[1]; Z = px[2];
-            mp = (a.perm[q] >= a.n_pts_fix) ? 1.0 : 0.0;
+            mp = point_mask(a.perm, a.n_pts_fix, q);
         }
         double t[3] = {0.0, 0.0, 0.0};
         int pos = su.pos;
-        const int io0 = has ? a.ipt_ofs[q] : 0;
+        const int io0 = (has && (MODEL == RPC || a.sc)) ? a.ipt_ofs[q] : 0;  // only read where it is used: stored RPC rows, row scales
         if constexpr (MODEL == AFFINE) {
             constexpr int D = SATBA_CAM_PF;
             int cq[D];
@@ -1618,13 +1647,13 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
             for (int d = 0; d < D; ++d) {
                 const int kd = su.slot(d);
                 cq[d] = 0; sq[d] = make_double2(1.0, 1.0);
-                if (kd < cnt) { cq[d] = a.e_cam[pos + d * su.step]; if (a.sc) sq[d] = a.sc[io0 + kd]; }
+                if (kd < cnt) { cq[d] = cams(pos + d * su.step); if (a.sc) sq[d] = a.sc[io0 + kd]; }
             }
             for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
                 const int k = su.slot(tt), kn = su.slot(tt + D);
                 int cn = 0;
                 double2 sn = make_double2(1.0, 1.0);
-                if (kn < cnt) { cn = a.e_cam[pos + D * su.step]; if (a.sc) sn = a.sc[io0 + kn]; }
+                if (kn < cnt) { cn = cams(pos + D * su.step); if (a.sc) sn = a.sc[io0 + kn]; }
                 __builtin_amdgcn_sched_barrier(0);
                 const int cam = cq[0];
                 const double2 s2 = sq[0];
@@ -1646,7 +1675,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub(ObsArgs a, const double*
             for (int tt = 0; tt < su.nt; ++tt, pos += su.step) {
                 const int k = su.slot(tt);
                 if (k < cnt) {
-                    const int cam = a.e_cam[pos];
+                    const int cam = cams(pos);
                     ObsEval<MODEL, NP, true> e;
                     e.jac(a, io0 + k, cam, mp, T.cc(cam), T.tab(cam), X, Y, Z);
                     double u0 = 0.0, u1 = 0.0;

@@ -11,7 +11,7 @@
 //              is stored contiguously, so "observation k of my point" is a coalesced access for the wave:
 //                  pos(q, k) = slice_base[q / 64] + 64 k + q % 64,       k < pt_cnt[q]
 //              A slice is as long as its longest track; because the points are sorted by length the padding is a few
-//              slots at the boundaries between length classes (e_cam = -1 there).  Every per-observation array of the
+//              slots at the boundaries between length classes (e_cam = -1, e_cam8 = 0xFF there).  Every per-observation array of the
 //              solver (residuals, row scales, stored RPC Jacobian blocks) uses these positions.
 //   io         internal point-major observation index io(q, k) = ipt_ofs[q] + k: the observations of a point are neighbours.
 //              Per-observation data that the Schur kernels GATHER (Jacobian row scales, stored RPC blocks) is kept in this
@@ -35,6 +35,8 @@ struct Layout {
     int C = 1;                              // point-range chunks of the pair lists
     int *perm = nullptr, *rank = nullptr, *pt_cnt = nullptr, *slice_base = nullptr;
     int* e_cam = nullptr;
+    unsigned char* e_cam8 = nullptr;  // P (+ 64): e_cam in one byte, padding 0xFF -- what the point kernels stream; built for M <= 255
+                                      // (0xFF is then no camera), null otherwise.  Every other reader keeps e_cam
     double2* e_obs = nullptr;
     double* e_w = nullptr;
     int *obs_pos = nullptr, *pts_ind = nullptr;
@@ -133,13 +135,14 @@ __global__ void k_lay_rank(int N, const int* __restrict__ perm, const int* __res
 __global__ void k_lay_fill_ell(long long K, const int* __restrict__ cam, const int* __restrict__ pt, const double2* __restrict__ obs,
                                const double* __restrict__ w, const int* __restrict__ ofs, const int* __restrict__ rank,
                                const int* __restrict__ slice_base, const int* __restrict__ ipt_ofs, int* __restrict__ e_cam,
-                               double2* __restrict__ e_obs, double* __restrict__ e_w, int* __restrict__ obs_pos,
-                               int* __restrict__ io_cam, int* __restrict__ io_pos, int* __restrict__ io_pt) {
+                               unsigned char* __restrict__ e_cam8, double2* __restrict__ e_obs, double* __restrict__ e_w,
+                               int* __restrict__ obs_pos, int* __restrict__ io_cam, int* __restrict__ io_pos, int* __restrict__ io_pt) {
     for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < K; o += (long long)gridDim.x * blockDim.x) {
         const int p = pt[o], q = rank[p], k = (int)(o - ofs[p]);
         const int pos = slice_base[q >> 6] + 64 * k + (q & 63);
         const int c = cam[o];
         e_cam[pos] = c;
+        if (e_cam8) e_cam8[pos] = (unsigned char)c;  // (null: more than 255 cameras)
         e_obs[pos] = obs[o];
         e_w[pos] = w[o];
         obs_pos[o] = pos;

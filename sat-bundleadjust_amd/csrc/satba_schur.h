@@ -91,7 +91,7 @@ __global__ __launch_bounds__(VINV_THREADS) void k_vinv(int N, double lam, const 
     const double o0 = o[0], o1 = o[1], o2 = o[2], o3 = o[3], o4 = o[4], o5 = o[5];
     const double x0 = xp[3 * (size_t)p], x1 = xp[3 * (size_t)p + 1], x2 = xp[3 * (size_t)p + 2];
     const double g0 = gp[3 * (size_t)p], g1 = gp[3 * (size_t)p + 1], g2 = gp[3 * (size_t)p + 2];
-    const double mp = (perm[p] >= n_pts_fix) ? 1.0 : 0.0;
+    const double mp = point_mask(perm, n_pts_fix, p);
     double2* t = s_t[wave];
     const int n_here = min(64, N - p0);  // points of this wave
     // records: 8 pieces per point (6 used), LDS row stride 9 pieces
