@@ -417,6 +417,25 @@ int satba_match_pairs(int32_t n_cam, const int64_t *n_kp, const float *const *fe
 int satba_matches_fetch(satba_matches *m, int64_t *pair_ofs, int32_t *kp_i, int32_t *kp_j);
 void satba_matches_destroy(satba_matches *m);
 
+/* ---- SIFT matching inside a UTM window, the matcher for pairs without a usable fundamental matrix (ft_match.py:151-160, 396-463,
+ * locally_match_SIFT_utm_coords; its C routine is in neither tree, so the rule is fixed here).  Exactly as in satba_match_pairs: the
+ * inputs, padding rows, the selection by the pair's box, the upload of each named image once, the satba_matches handle with
+ * satba_matches_fetch / satba_matches_destroy, the output order, counts[0..3] (path: 0 integer, 1 float32), SATBA_MATCH_FLOAT=1,
+ * kernel_ms and the argument errors.  Detected by its presence; the version number stays.
+ * Per pair (im_i, im_j), for a selected keypoint i of im_i: its candidates are the selected keypoints j of im_j with
+ * fabs(east_i - east_j) < rx and fabs(north_i - north_j) < ry, in float64, each difference rounded once, strict; a keypoint of im_j
+ * outside the pair's box is no candidate however near it lies.  rx, ry may be +inf; NaN or a value <= 0 is SATBA_E_ARG.
+ * d(i, j) = sum (a - b)^2 over the 128 descriptor values: exact in integers where all descriptors are integers in [0, 255],
+ * otherwise in float32 accumulated in index order without fused multiply-add.  distA = the smallest d over the candidates, among
+ * equals the lowest j (a reduction on the pair (d, j): the order of the visit does not matter).  (i, j) is a match when there is a
+ * candidate and float32(distA) < float32(thr) * float32(thr); there is no relative test and no second nearest.  With rx = ry = +inf
+ * this is satba_match_pairs with F5 = NULL and relative = 0.
+ * counts (host, 5 x int64): [0..3] as above, [4] the (i, j) that passed the window test, summed over all pairs.
+ * n_pairs == 0 returns 0 with an empty handle; fewer than 2^24 pairs per call. */
+int satba_match_window(int32_t n_cam, const int64_t *n_kp, const float *const *features, const double *const *utm, int32_t n_pairs,
+                       const int32_t *pairs, const double *boxes, double rx, double ry, float thr, satba_matches **out,
+                       int64_t *counts /* 5 */, int32_t device, float *kernel_ms);
+
 /* ---- SIFT detection and description of one image, the step in front of the matching (ref:s2p/sift.py keypoints_from_nparray,
  * i.e. sift() of ref:3rdparty/sift/simd/sift4ctypes.cpp:71-123: "Anatomy of the SIFT method" with delta_min 0.5, sigma_min 0.8,
  * sigma_in 0.5, 36 orientation bins, 4 x 4 x 8 descriptors, 5 interpolation steps, edge 10, lambda_ori 1.5, lambda_des 6, t 0.8).

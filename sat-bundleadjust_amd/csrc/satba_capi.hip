@@ -30,6 +30,7 @@
 #include "satba_tracks.h"
 #include "satba_ftracks.h"
 #include "satba_match.h"
+#include "satba_window.h"
 #include "satba_sift.h"
 #include "satba_rpcfit.h"
 #include "satba_camapprox.h"
@@ -1752,6 +1753,7 @@ int satba_time_kernel(satba_problem* p, int32_t phase, int32_t reps, float* ms_a
 #include "satba_tracks_api.inc"
 #include "satba_ftracks_api.inc"
 #include "satba_match_api.inc"
+#include "satba_window_api.inc"
 #include "satba_sift_api.inc"
 
 }  // extern "C"

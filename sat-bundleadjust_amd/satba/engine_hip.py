@@ -39,7 +39,7 @@ SYMBOLS = [
     "satba_utm_filter", "satba_keypoints_utm",
     "satba_track_keys", "satba_track_connectivity", "satba_select_tracks",
     "satba_ftracks_build", "satba_ftracks_fetch", "satba_ftracks_destroy", "satba_tracks_have_pair",
-    "satba_match_pairs", "satba_matches_fetch", "satba_matches_destroy",
+    "satba_match_pairs", "satba_matches_fetch", "satba_matches_destroy", "satba_match_window",
     "satba_sift_detect", "satba_sift_fetch", "satba_sift_fetch_plane", "satba_sift_destroy",
 ]
 
@@ -188,6 +188,8 @@ def load_library(path=None):
     lib.satba_matches_fetch.argtypes = [C.c_void_p, _lp, _ip, _ip]
     lib.satba_matches_destroy.argtypes = [C.c_void_p]
     lib.satba_matches_destroy.restype = None
+    lib.satba_match_window.argtypes = [C.c_int32, _lp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, _ip, _dp, C.c_double, C.c_double, C.c_float,
+                                       C.POINTER(C.c_void_p), _lp, C.c_int32, _fp]
     lib.satba_sift_detect.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _lp,
                                       C.c_int32, _fp]
     lib.satba_sift_fetch.argtypes = [C.c_void_p, _fp]

@@ -31,7 +31,14 @@ in one device call, with max_err = FT_ransac (0.3), 1000 trials and `ransac_seed
 boolean mask is taken as before; None (the default) filters nothing.  `ransac_fundamental`, `geometric_filtering` and
 `inliers_mask_from_fundamental_matrix` are the pieces on their own, the last two under the reference's names.
 
-Not reproduced: the pairwise .npy cache files are not read or written, and only "epipolar_based" and "bruteforce" are matched here.
+"local_window" (ref:ft_match.py:151-160, 396-463) is the matcher for pairs without a usable fundamental matrix: a keypoint is
+compared only with the keypoints of the other image within FT_local_radius metres (30; the reference hard-codes it) on the ground,
+under the absolute threshold FT_abs_thr (250), with no relative test.  `match_pairs_window` is the device call (satba_match_window:
+the rule of include/satba.h, csrc/satba_window.h, DESIGN.md 4q -- the reference's C routine is in neither tree);
+`locally_match_SIFT_utm_coords` is the one-pair function under the reference's name.
+
+Not reproduced: the pairwise .npy cache files are not read or written, and of the reference's matching methods "flann" and
+"lightglue" (foreign libraries) are not matched here.
 """
 import ctypes as ct
 
@@ -48,7 +55,7 @@ _lp = ct.POINTER(ct.c_int64)
 _fp = ct.POINTER(ct.c_float)
 _bp = ct.POINTER(ct.c_uint8)
 EPIPOLAR_THR = 20.0  # ref:ft_s2p.py:145
-METHODS = ("epipolar_based", "bruteforce")
+METHODS = ("epipolar_based", "bruteforce", "local_window")
 
 
 # ----------------------------------------------------------------------------- convex polygons (in place of shapely)
@@ -211,14 +218,9 @@ def _load(a, dtype, cols):
     return a
 
 
-def match_pairs(pairs, features, utm_coords, boxes, F=None, thr=0.6, epi_thr=EPIPOLAR_THR, relative=True, device=None, return_info=False):
-    """
-    satba_match_pairs (include/satba.h): all pairs in one call.  pairs (n, 2) image indices; features / utm_coords: per image an
-    (n_kp, 132) / (n_kp, 2) array or .npy path (images no pair names are not loaded); boxes (n, 4) = min_east, max_east, min_north,
-    max_north; F: None (no gate) or per pair a 3 x 3 matrix (or its five coefficients).  Returns pair_ofs (n + 1), kp_i, kp_j: the
-    matches of pair p are rows pair_ofs[p] : pair_ofs[p + 1], kp_i ascending.  With return_info also a dict: n_selected,
-    n_empty_pairs, path ("int8" | "float32"), kernel_ms.
-    """
+def _match_inputs(pairs, features, utm_coords, boxes):
+    """the arguments that satba_match_pairs and satba_match_window share, checked and laid out for the call (the arrays are returned
+    so that they outlive it)"""
     pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
     n_pairs, n_cam = pairs.shape[0], len(features)
     if len(utm_coords) != n_cam:
@@ -228,11 +230,6 @@ def match_pairs(pairs, features, utm_coords, boxes, F=None, thr=0.6, epi_thr=EPI
     boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 4))
     if boxes.shape[0] != n_pairs:
         raise ValueError("one box per pair")
-    F5 = None
-    if F is not None:
-        if len(F) != n_pairs:
-            raise ValueError("one fundamental matrix per pair")
-        F5 = np.ascontiguousarray(np.array([_f5(f) for f in F], dtype=np.float64).reshape(-1, 5))
     used = set(int(c) for c in pairs.reshape(-1))
     feats = [_load(features[c], np.float32, 132) if c in used else None for c in range(n_cam)]
     utms = [_load(utm_coords[c], np.float64, 2) if c in used else None for c in range(n_cam)]
@@ -244,23 +241,81 @@ def match_pairs(pairs, features, utm_coords, boxes, F=None, thr=0.6, epi_thr=EPI
     fptr = (ct.c_void_p * n_cam)(*[a.ctypes.data if a is not None else None for a in feats])
     uptr = (ct.c_void_p * n_cam)(*[a.ctypes.data if a is not None else None for a in utms])
     p32 = np.ascontiguousarray(pairs, dtype=np.int32)
+    return n_cam, n_kp, fptr, uptr, n_pairs, p32, boxes, (feats, utms)
+
+
+def _fetch_matches(lib, handle, n, n_pairs):
+    try:
+        pair_ofs = np.zeros(n_pairs + 1, dtype=np.int64)
+        kp_i, kp_j = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        E._check(lib, lib.satba_matches_fetch(handle, pair_ofs.ctypes.data_as(_lp), E._ptr(kp_i, E._ip), E._ptr(kp_j, E._ip)))
+    finally:
+        lib.satba_matches_destroy(handle)
+    return pair_ofs, kp_i, kp_j
+
+
+def _match_info(counts, ms):
+    return {"n_selected": int(counts[1]), "n_empty_pairs": int(counts[2]), "path": ("int8", "float32")[int(counts[3])], "kernel_ms": ms.value}
+
+
+def match_pairs(pairs, features, utm_coords, boxes, F=None, thr=0.6, epi_thr=EPIPOLAR_THR, relative=True, device=None, return_info=False):
+    """
+    satba_match_pairs (include/satba.h): all pairs in one call.  pairs (n, 2) image indices; features / utm_coords: per image an
+    (n_kp, 132) / (n_kp, 2) array or .npy path (images no pair names are not loaded); boxes (n, 4) = min_east, max_east, min_north,
+    max_north; F: None (no gate) or per pair a 3 x 3 matrix (or its five coefficients).  Returns pair_ofs (n + 1), kp_i, kp_j: the
+    matches of pair p are rows pair_ofs[p] : pair_ofs[p + 1], kp_i ascending.  With return_info also a dict: n_selected,
+    n_empty_pairs, path ("int8" | "float32"), kernel_ms.
+    """
+    n_cam, n_kp, fptr, uptr, n_pairs, p32, boxes, _keep = _match_inputs(pairs, features, utm_coords, boxes)
+    F5 = None
+    if F is not None:
+        if len(F) != n_pairs:
+            raise ValueError("one fundamental matrix per pair")
+        F5 = np.ascontiguousarray(np.array([_f5(f) for f in F], dtype=np.float64).reshape(-1, 5))
     lib = E.load_library()
     handle, ms = ct.c_void_p(None), ct.c_float(0.0)
     counts = np.zeros(4, dtype=np.int64)
     E._check(lib, lib.satba_match_pairs(n_cam, n_kp.ctypes.data_as(_lp), fptr, uptr, n_pairs, E._ptr(p32, E._ip), E._ptr(boxes),
                                         E._ptr(F5) if F5 is not None else None, float(thr), float(epi_thr), 1 if relative else 0, ct.byref(handle),
                                         counts.ctypes.data_as(_lp), _device(device), ct.byref(ms)))
-    try:
-        n = int(counts[0])
-        pair_ofs = np.zeros(n_pairs + 1, dtype=np.int64)
-        kp_i, kp_j = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        E._check(lib, lib.satba_matches_fetch(handle, pair_ofs.ctypes.data_as(_lp), E._ptr(kp_i, E._ip), E._ptr(kp_j, E._ip)))
-    finally:
-        lib.satba_matches_destroy(handle)
+    pair_ofs, kp_i, kp_j = _fetch_matches(lib, handle, int(counts[0]), n_pairs)
     if return_info:
-        return pair_ofs, kp_i, kp_j, {"n_selected": int(counts[1]), "n_empty_pairs": int(counts[2]), "path": ("int8", "float32")[int(counts[3])],
-                                      "kernel_ms": ms.value}
+        return pair_ofs, kp_i, kp_j, _match_info(counts, ms)
     return pair_ofs, kp_i, kp_j
+
+
+def match_pairs_window(pairs, features, utm_coords, boxes, radius=30.0, thr=250.0, device=None, return_info=False):
+    """
+    satba_match_window (include/satba.h): the windowed match of all pairs in one call.  Arguments and results as `match_pairs`;
+    radius: the window's half-width on the ground in metres, a scalar or (rx, ry), +inf allowed; thr: the absolute threshold on the
+    descriptor distance.  A keypoint of the first image is compared with the keypoints of the second inside the pair's box whose
+    easting differs by less than rx and whose northing by less than ry; the nearest matches when its distance is below thr ** 2.
+    The info dict additionally holds n_candidates, the (i, j) that passed the window test summed over all pairs.
+    """
+    r = np.asarray(radius, dtype=np.float64).reshape(-1)
+    if r.size not in (1, 2):
+        raise ValueError("radius must be a scalar or (rx, ry), got {!r}".format(radius))
+    rx, ry = float(r[0]), float(r[-1])
+    n_cam, n_kp, fptr, uptr, n_pairs, p32, boxes, _keep = _match_inputs(pairs, features, utm_coords, boxes)
+    lib = E.load_library()
+    if not hasattr(lib, "satba_match_window"):
+        raise OSError("libsatba_hip.so has no satba_match_window: rebuild it (make -C sat-bundleadjust_amd/csrc)")
+    handle, ms = ct.c_void_p(None), ct.c_float(0.0)
+    counts = np.zeros(5, dtype=np.int64)
+    E._check(lib, lib.satba_match_window(n_cam, n_kp.ctypes.data_as(_lp), fptr, uptr, n_pairs, E._ptr(p32, E._ip), E._ptr(boxes), rx, ry, float(thr),
+                                         ct.byref(handle), counts.ctypes.data_as(_lp), _device(device), ct.byref(ms)))
+    pair_ofs, kp_i, kp_j = _fetch_matches(lib, handle, int(counts[0]), n_pairs)
+    if return_info:
+        return pair_ofs, kp_i, kp_j, dict(_match_info(counts, ms), n_candidates=int(counts[4]))
+    return pair_ofs, kp_i, kp_j
+
+
+def _match_by_method(method, pairs, feats, utms, boxes, Fs, tracks_config, device):
+    """the device match of `pairs` by the configured method: (pair_ofs, kp_i, kp_j, info)"""
+    if method == "local_window":
+        return match_pairs_window(pairs, feats, utms, boxes, radius=tracks_config.get("FT_local_radius", 30.0), thr=tracks_config.get("FT_abs_thr", 250),
+                                  device=device, return_info=True)
+    return match_pairs(pairs, feats, utms, boxes, F=Fs, thr=tracks_config.get("FT_rel_thr", 0.6), device=device, return_info=True)
 
 
 def _method(tracks_config):
@@ -482,8 +537,7 @@ def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygo
     Fs = [F] if method == "epipolar_based" else None
     if method == "epipolar_based" and F is None:
         raise ValueError("epipolar_based matching needs the fundamental matrix of the pair")
-    ofs, kp_i, kp_j, info = match_pairs([(0, 1)], [fi, fj], [ui, uj], [box], F=Fs, thr=tracks_config.get("FT_rel_thr", 0.6), device=device,
-                                        return_info=True)
+    ofs, kp_i, kp_j, info = _match_by_method(method, [(0, 1)], [fi, fj], [ui, uj], [box], Fs, tracks_config, device)
     if info["n_empty_pairs"]:
         return None, [0, 0, 0]
     m_ij, _, alive, keep, _ = _rename_and_filter(ofs, kp_i, kp_j, [(0, 1)], [fi, fj], [ui, uj], canonical, geometric_filter, tracks_config, ransac_seed,
@@ -496,11 +550,32 @@ def match_kp_within_utm_polygon(features_i, features_j, utm_i, utm_j, utm_polygo
     return (m_ij if m_ij.shape[0] else None), n
 
 
+def locally_match_SIFT_utm_coords(features_i, features_j, utm_i, utm_j, radius=30, sift_thr=250, ransac_thr=0.3, seed=0, device=None):
+    """ref:ft_match.py:396-463: the windowed match over all rows of two images (an infinite box), then `geometric_filtering` (the
+    device RANSAC).  Returns (matches_ij (M, 2) or None, n_matches, n_matches_after_geofilt).  The reference adds 10e6 to every
+    negative northing; so does this, on copies: the reference writes the shift, and then its registered coordinates, into its
+    caller's arrays, which is not reproduced -- no argument is written to."""
+    fi, fj = _load(features_i, np.float32, 132), _load(features_j, np.float32, 132)
+    ui, uj = np.array(_load(utm_i, np.float64, 2)), np.array(_load(utm_j, np.float64, 2))  # copies
+    for u in (ui, uj):
+        with np.errstate(invalid="ignore"):
+            u[u[:, 1] < 0, 1] += 10e6
+    inf = np.inf
+    ofs, kp_i, kp_j = match_pairs_window([(0, 1)], [fi, fj], [ui, uj], [(-inf, inf, -inf, inf)], radius=radius, thr=sift_thr, device=device)
+    matches_ij = np.stack([kp_i, kp_j], axis=1).astype(np.int64)
+    n_matches = matches_ij.shape[0]
+    if n_matches == 0:
+        return None, 0, 0
+    matches_ij = geometric_filtering(fi, fj, matches_ij, ransac_thr, seed=seed, device=device)
+    return matches_ij, n_matches, (0 if matches_ij is None else matches_ij.shape[0])
+
+
 def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_config, F=None, canonical=True, geometric_filter=None,
                        device=None, return_info=False, ransac_seed=0):
     """
     ref:ft_match.py:250-339.  features / utm_coords: per image an array or a .npy path; footprints: per image a dict with a
-    "geojson" polygon in UTM coordinates (convex).  F: per pair a 3 x 3 fundamental matrix ("epipolar_based").  Returns the M x 4
+    "geojson" polygon in UTM coordinates (convex).  F: per pair a 3 x 3 fundamental matrix ("epipolar_based"; "bruteforce" and
+    "local_window" need none -- the latter reads FT_local_radius and FT_abs_thr).  Returns the M x 4
     int64 array (kp_i, kp_j, im_i, im_j), pairs in the given order; a pair whose footprints share no area gives no rows.
     geometric_filter: None, a callable per pair, or "ransac": the device RANSAC over all pairs in one call (module docstring), whose
     kernel time return_info reports as "ransac_kernel_ms".  The renaming and the UTM filter take all pairs at once; the filter is one
@@ -523,8 +598,7 @@ def match_stereo_pairs(pairs_to_match, features, footprints, utm_coords, tracks_
             raise ValueError("a pair names an image outside 0..{}".format(len(features) - 1))
         feats = [_load(features[c], np.float32, 132) if c in used else None for c in range(len(features))]  # loaded once
         utms = [_load(utm_coords[c], np.float64, 2) if c in used else None for c in range(len(utm_coords))]
-        ofs, kp_i, kp_j, info = match_pairs([pairs[k] for k in live], feats, utms, [boxes[k] for k in live], F=Fs,
-                                            thr=tracks_config.get("FT_rel_thr", 0.6), device=device, return_info=True)
+        ofs, kp_i, kp_j, info = _match_by_method(method, [pairs[k] for k in live], feats, utms, [boxes[k] for k in live], Fs, tracks_config, device)
         m_ij, im, _, keep, times = _rename_and_filter(ofs, kp_i, kp_j, [pairs[k] for k in live], feats, utms, canonical, geometric_filter, tracks_config,
                                                       ransac_seed, device)
         out = np.concatenate([m_ij, im], axis=1)[keep]
